@@ -2,7 +2,14 @@
 """Benchmark of the hot path: rasteriser forward+backward (incl. pose Jacobian) on the
 SYN-C workload of BASELINE.md §4 (640x480, 300k Gaussians, SH degree 0).
 
-    python bench.py --gpus N --steps K --warmup W [--workload synC|replica]
+    python bench.py --gpus N --steps K --warmup W [--workload synC|replica] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline (`value`, `ms_per_step`);
+with `--dump-outputs DIR` it first writes what the last timed step returned to its caller (image,
+depth, opacity, radii, n_touched, loss and every gradient) as DIR/<name>.npy.  Everything else -
+the per-kernel roofline pass, the sustained rate, the default-engine figure, the CPU baseline, the
+tracking / map-update / mapping / SLAM / knn legs and the multi-rank exchange figures - runs only
+with `--full`.
 
 N = 1: one view per step through the autograd binding (what MonoGS's render() +
 loss.backward() exercises).
@@ -23,9 +30,8 @@ Backend: "nccl" (= RCCL) when the node has >= N GPUs, otherwise a gloo rehearsal
 ranks share the GPU(s) and the flat buffer is staged through host memory (functional check of
 the exchange on a 1-GPU box; not a performance number - the JSON says which one ran).
 
-Rank 0 prints ONE JSON line (contract in the task statement) with `roofline` (dominant
-kernel, HIP-event timed inside the library on the launch stream) and `cpu_baseline`
-(N = 1 only).
+Rank 0 prints ONE JSON line; with `--full` it carries `roofline` (dominant kernel, HIP-event
+timed inside the library on the launch stream) and `cpu_baseline` (N = 1 only).
 """
 from __future__ import annotations
 
@@ -67,12 +73,24 @@ def parse(argv=None):
     ap.add_argument("--no-slam", action="store_true")
     ap.add_argument("--sustain-seconds", type=float, default=2.0)
     ap.add_argument("--lean", action="store_true",
-                    help="headline + roofline only (for rocprofv3 runs): no cpu baseline, tracking, "
+                    help="with --full: headline + roofline only (for rocprofv3 runs): no cpu baseline, tracking, "
                          "mapping, SLAM or sustained legs")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beyond the headline: roofline pass, sustained rate, default-engine "
+                         "figure, cpu baseline, tracking / map-update / mapping / SLAM / knn legs, multi-rank "
+                         "exchange figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64)")
     args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.lean:
         args.no_cpu_baseline = args.no_tracking = args.no_mapping = args.no_slam = True
         args.sustain_seconds = 0.0
+    if not args.full:      # a plain run: the headline only
+        args.no_cpu_baseline = args.no_tracking = args.no_mapping = args.no_slam = True
+        args.sustain_seconds = 0.0
+        args.profile_steps = 0
     return args
 
 
@@ -289,6 +307,32 @@ def exchange_model(world, nbytes):
                        "reduce-scatter / all-gather over the 7 links (DESIGN.md section 6)"}
 
 
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(outdir, arrays, n_gaussians):
+    """Write `arrays` (name -> tensor) as outdir/<name>.npy: floating point as float32, integers as float64 (exact).
+    Above DUMP_BYTES_MAX in all, the per-Gaussian arrays (first dimension = n_gaussians) keep only a fixed, seeded
+    sample of rows, whose indices go to gaussian_sample_index.npy."""
+    import numpy as np
+    import torch
+    host = {k: v.detach().cpu() for k, v in arrays.items()}
+    host = {k: v.double() if not v.is_floating_point() else v.float() for k, v in host.items()}
+    per_g = [k for k, v in host.items() if v.dim() > 0 and v.shape[0] == n_gaussians]
+    total = sum(v.numel() * v.element_size() for v in host.values())
+    if total > DUMP_BYTES_MAX:
+        rest = total - sum(host[k].numel() * host[k].element_size() for k in per_g)
+        row = sum(host[k][0].numel() * host[k].element_size() for k in per_g) + 8
+        keep = max(1, min(n_gaussians, (DUMP_BYTES_MAX - 4096 - rest) // row))     # 4 KB for the .npy headers
+        idx = torch.randperm(n_gaussians, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+        for k in per_g:
+            host[k] = host[k][idx]
+        host["gaussian_sample_index"] = idx.double()
+    os.makedirs(outdir, exist_ok=True)
+    for k, v in host.items():
+        np.save(os.path.join(outdir, k + ".npy"), v.numpy())
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     args = parse(argv)
@@ -360,8 +404,9 @@ def main(argv=None):
     if bucket is not None and world == 1:
         bucket.force_collective = True
     ex_events = []
+    last = {}      # what the last timed step handed back to its caller (--dump-outputs)
 
-    def step(exchange=True, timed_exchange=False):
+    def step(exchange=True, timed_exchange=False, keep=False):
         for p in params:
             p.grad = None
         theta.grad = None
@@ -381,6 +426,11 @@ def main(argv=None):
             if timed_exchange:
                 e1.record()
                 ex_events.append((e0, e1))
+        if keep:
+            last.update(image=img, depth=dep, opacity=opa, radii=radii, n_touched=nt, loss=loss.reshape(1),
+                        grad_means3D=params[0].grad, grad_scales=params[1].grad, grad_rotations=params[2].grad,
+                        grad_opacities=params[3].grad, grad_shs=params[4].grad, grad_means2D=m2d.grad,
+                        grad_rho=rho.grad, grad_theta=theta.grad)
         return loss
 
     def barrier():
@@ -388,11 +438,11 @@ def main(argv=None):
             dist.barrier()
         torch.cuda.synchronize()
 
-    def timed(k, **kw):
+    def timed(k, keep_last=False, **kw):
         barrier()
         t0 = time.perf_counter()
-        for _ in range(k):
-            step(**kw)
+        for i in range(k):
+            step(keep=keep_last and i == k - 1, **kw)
         barrier()
         return time.perf_counter() - t0
 
@@ -420,13 +470,16 @@ def main(argv=None):
         torch.autograd.set_multithreading_enabled(engine_mt)
     else:
         engine_mt = False
-    dt = max_over_ranks(timed(args.steps))
+    dt = max_over_ranks(timed(args.steps, keep_last=args.dump_outputs is not None))
     ms_per_step = dt / args.steps * 1e3
     value = world * args.steps / dt          # views (frames) per second, whole job
+    if last and rank == 0:
+        dump_outputs(args.dump_outputs, last, N)
+    last.clear()
     # what a MonoGS user gets without touching the autograd engine setting: the same K steps with
     # PyTorch's default (worker-thread) engine, first-class beside the calibrated figure
     value_default_engine = None
-    if not distributed:
+    if args.full and not distributed:
         if engine_mt:
             value_default_engine = value
         else:
@@ -439,7 +492,7 @@ def main(argv=None):
 
     # ---- multi-rank extras: exchange cost and per-rank compute, measured separately ----
     multi = None
-    if distributed:
+    if args.full and distributed:
         k = min(args.steps, 50)
         t_compute = timed(k, exchange=False) / k * 1e3           # this rank's fwd+loss+bwd alone
         timed(k, timed_exchange=True)
@@ -607,7 +660,7 @@ def main(argv=None):
     if single and not args.no_slam:
         from monogs_amd.bench_legs import bench_slam_surrogate
         slam = bench_slam_surrogate(dev)
-    knn = bench_knn(dev) if (rank == 0 and not distributed and not args.lean) else None
+    knn = bench_knn(dev) if (args.full and rank == 0 and not distributed and not args.lean) else None
 
     if rank == 0:
         out = {
@@ -615,7 +668,7 @@ def main(argv=None):
             "value": round(value, 2), "unit": "frames/s", "n_gpus": world, "steps": args.steps,
             "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
             "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-            "data": "synthetic",
+            "data": "synthetic", "full": bool(args.full),
             "config": {"workload": f"{wname}: {N} Gaussians @ {W}x{H}, SH degree 0, fwd+bwd incl. "
                                    "pose Jacobian through the autograd binding",
                        "pairs_D": D, "views_per_step": world, "autograd_multithreading": bool(engine_mt),

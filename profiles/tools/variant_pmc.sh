@@ -1,24 +1,27 @@
 #!/bin/bash
 # A/B of library variants under scratch/variants (profiles/tools/build_variant.sh): for each one
-#   * bench.py --lean --steps 50 (fps, kernels_us from the in-library HIP events)
+#   * bench.py --full --lean --steps 50 (fps, kernels_us from the in-library HIP events)
 #   * rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE passes (separate runs) -> corrected HBM bytes per launch
 #     of the blend kernels, (2 FETCH + WRITE) * 1024 (MI355X_MICROARCH.md, HBM section)
-# usage (through gpurun, from the repo root): profiles/tools/variant_pmc.sh [tag]   -> gpurun_out/<tag>_variants.txt
+# usage (from the repo root): profiles/tools/variant_pmc.sh [tag]   -> $VARIANT_OUT/<tag>_variants.txt
+# (VARIANT_OUT defaults to /tmp/variant_pmc)
 tag=${1:-r04}
 root=${GRAFT_REPO_ROOT:-$(pwd)}
 cd /tmp && export TMPDIR=/tmp
 cd "$root"
-out=gpurun_out/${tag}_variants.txt
+vo=${VARIANT_OUT:-/tmp/variant_pmc}
+mkdir -p "$vo"
+out=$vo/${tag}_variants.txt
 : > $out
 for f in scratch/variants/lib_*.so; do
   n=$(basename $f .so)
   export MGS_LIB_PATH=$PWD/$f
-  python3 bench.py --lean --steps 50 --warmup 10 > gpurun_out/${tag}_var_$n.json 2> gpurun_out/${tag}_var_$n.err
-  d=gpurun_out/${tag}_pmc_$n
+  python3 bench.py --full --lean --steps 50 --warmup 10 > $vo/${tag}_var_$n.json 2> $vo/${tag}_var_$n.err
+  d=$vo/${tag}_pmc_$n
   rm -rf $d; mkdir -p $d
-  rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $d/fetch -o run -- python3 bench.py --steps 20 --warmup 5 --lean --profile-steps 0 > $d/fetch.log 2>&1
-  rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $d/write -o run -- python3 bench.py --steps 20 --warmup 5 --lean --profile-steps 0 > $d/write.log 2>&1
-  python3 - "$n" "$d" "gpurun_out/${tag}_var_$n.json" >> $out <<'PY'
+  rocprofv3 --kernel-trace --output-format csv --pmc FETCH_SIZE -d $d/fetch -o run -- python3 bench.py --steps 20 --warmup 5 --full --lean --profile-steps 0 > $d/fetch.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv --pmc WRITE_SIZE -d $d/write -o run -- python3 bench.py --steps 20 --warmup 5 --full --lean --profile-steps 0 > $d/write.log 2>&1
+  python3 - "$n" "$d" "$vo/${tag}_var_$n.json" >> $out <<'PY'
 import collections, csv, glob, json, sys
 n, d, j = sys.argv[1:4]
 try:

@@ -97,7 +97,7 @@ def test_bench_gpus_2_starts_two_ranks(built):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT"):
         env.pop(k, None)
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1",
-                        "--gaussians", "20000", "--width", "320", "--height", "240", "--profile-steps", "0",
+                        "--full", "--gaussians", "20000", "--width", "320", "--height", "240", "--profile-steps", "0",
                         "--no-cpu-baseline", "--no-tracking", "--no-slam", "--sustain-seconds", "0",
                         "--mapping-gaussians", "30000", "--mapping-iters", "6"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
@@ -251,7 +251,7 @@ def test_bench_rccl_backend_with_a_one_rank_group(built):
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1",
                         "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"),
                         "--gpus", "1", "--steps", "3", "--warmup", "1", "--gaussians", "20000", "--width", "320",
-                        "--height", "240", "--lean", "--profile-steps", "0"],
+                        "--height", "240", "--full", "--lean", "--profile-steps", "0"],
                        env=env, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
