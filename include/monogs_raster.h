@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 8
+#define MGS_ABI_VERSION 9
 
 typedef enum mgs_status {
   MGS_OK = 0,
@@ -203,7 +203,8 @@ int32_t mgs_abi_version(void);
  * 8 = mgs_tracking_iter_args, 9 = mgs_sketch_residual_args, 10 = mgs_tracking_so_args,
  * 11 = mgs_adam_group, 12 = mgs_map_plan_args, 13 = mgs_gather_tensor, 14 = mgs_map_gather_args,
  * 15 = mgs_map_accum_args, 16 = mgs_map_activate_args, 17 = mgs_mapping_view_args,
- * 18 = mgs_map_finish_args, 19 = mgs_map_append_args);
+ * 18 = mgs_map_finish_args, 19 = mgs_map_append_args, 20 = mgs_ssim_loss_args,
+ * 21 = mgs_refine_view_args);
  * -1 for an unknown index.  Lets a foreign-language binding verify its struct mirrors. */
 int32_t mgs_struct_size(int32_t which);
 const char* mgs_status_string(int32_t status);
@@ -773,6 +774,58 @@ typedef struct mgs_map_append_args {
 } mgs_map_append_args;
 
 int32_t mgs_map_append(const mgs_map_append_args* args, void* stream);
+
+/* ---- colour refinement (utils/slam_backend.py:335-368) ------------------------------------ */
+
+/* Objective of BackEnd.color_refinement (slam_backend.py:355-358; loss_utils.py:21-22,63-101):
+ *   l1 = mean |image - gt|,  ssim = mean S (11x11 Gaussian window, sigma 1.5, per channel, zero padding,
+ *   C1 = 0.01^2, C2 = 0.03^2),  loss = w_l1 l1 + w_ssim (1 - ssim)
+ * over [C,H,W] (means over C H W), value and - unless grad_image is NULL - grad_image = g d loss / d image in ONE
+ * launch, g = *grad_out (NULL: 1).  `partial` holds mgs_ssim_loss_partial_count(C, H, W) floats; its last slot is
+ * an int ticket that must be zero when the FIRST call on the buffer is enqueued (every call restores it), so calls
+ * in stream order may share the buffer.  Deterministic: no float atomics. */
+typedef struct mgs_ssim_loss_args {
+  int32_t channels, height, width;
+  float w_l1, w_ssim;            /* 1 - lambda_dssim, lambda_dssim */
+  int32_t reserved0;
+  const float* image;            /* [C,H,W] */
+  const float* gt;               /* [C,H,W] */
+  const float* grad_out;         /* [1] upstream gradient or NULL (1) */
+  float* grad_image;             /* [C,H,W] out, or NULL: value only */
+  float* partial;                /* scratch, see above */
+  float* l1;                     /* [1] out, or NULL */
+  float* ssim;                   /* [1] out, or NULL */
+  float* loss;                   /* [1] out */
+} mgs_ssim_loss_args;
+
+/* Floats of mgs_ssim_loss_args.partial for a [C,H,W] image; -1 for a size the kernel is not built for. */
+int32_t mgs_ssim_loss_partial_count(int32_t channels, int32_t height, int32_t width);
+int32_t mgs_ssim_loss(const mgs_ssim_loss_args* args, void* stream);
+
+/* One view of one colour-refinement iteration (the body of slam_backend.py:341-365 up to the optimiser step) as a
+ * fixed launch sequence with no host round trip:
+ *   camera matrices from T (skipped when camera_matrices_valid) -> rasteriser forward at the caller's fixed pair
+ *   capacity -> mgs_ssim_loss(out_color, loss.gt) -> rasteriser backward in mapping mode (accum: gradients chained
+ *   through the activations, OVERWRITTEN; no regulariser, no densification statistics, no visibility) ->
+ *   max_radii2D = max(max_radii2D, radii) where radii > 0.
+ * No exposure is applied and no pose or exposure step is taken.  The caller steps the Gaussians' optimiser.
+ * loss.image / grad_image / grad_out / channels / height / width are filled in by the call; loss.gt, partial, loss
+ * (and optionally l1 / ssim) and the weights come from the caller.  accum.accumulate / add_regulariser /
+ * gradnorm_inc / denom_inc / radii_max / visibility are ignored (forced to 0 / NULL). */
+typedef struct mgs_refine_view_args {
+  mgs_forward_args fwd;
+  void* bwd;                     /* bwd_bytes of backward scratch */
+  float* grad_image;             /* [3,H,W] scratch */
+  float* grad_tau;               /* [6] scratch */
+  const float* T;                /* [4,4] world -> camera (the camera matrices are formed from it) */
+  mgs_ssim_loss_args loss;
+  mgs_map_accum_args accum;
+  float* max_radii2D;            /* [N] float */
+  int32_t camera_matrices_valid;
+  int32_t reserved0;
+} mgs_refine_view_args;
+
+int32_t mgs_refine_view_iteration(const mgs_refine_view_args* args, void* stream);
 
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.

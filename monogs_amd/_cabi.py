@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 # MGS_LIB_PATH: load another build of the SAME library (kernel experiments, the -DMGS_STAMP build)
 LIB_PATH = os.environ.get("MGS_LIB_PATH") or os.path.join(_HERE, "lib", "libmonogs_raster.so")
 
-ABI_VERSION = 8
+ABI_VERSION = 9
 
 EXPORTS = (
     "mgs_abi_version", "mgs_struct_size", "mgs_status_string", "mgs_raster_workspace_query",
@@ -26,6 +26,7 @@ EXPORTS = (
     "mgs_map_gather", "mgs_pack_mapping_grads", "mgs_sketch_assign", "mgs_sketch_residual",
     "mgs_tracking_iteration_second_order", "mgs_map_activate", "mgs_mapping_loss_partial_count",
     "mgs_mapping_loss_fused", "mgs_mapping_view_iteration", "mgs_map_finish_iteration", "mgs_map_append",
+    "mgs_ssim_loss_partial_count", "mgs_ssim_loss", "mgs_refine_view_iteration",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -190,6 +191,18 @@ class MapAppendArgs(C.Structure):
                 ("num_tensors", C.c_int32), ("rows_old", C.c_int64), ("rows_new", C.c_int64)]
 
 
+class SsimLossArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("channels", "height", "width")]
+                + [("w_l1", C.c_float), ("w_ssim", C.c_float), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("image", "gt", "grad_out", "grad_image", "partial", "l1", "ssim", "loss")])
+
+
+class RefineViewArgs(C.Structure):
+    _fields_ = [("fwd", ForwardArgs), ("bwd", _fp), ("grad_image", _fp), ("grad_tau", _fp), ("T", _fp),
+                ("loss", SsimLossArgs), ("accum", MapAccumArgs), ("max_radii2D", _fp),
+                ("camera_matrices_valid", C.c_int32), ("reserved0", C.c_int32)]
+
+
 _lib = None
 
 
@@ -289,6 +302,12 @@ def lib():
     L.mgs_map_finish_iteration.argtypes = [C.POINTER(MapFinishArgs), C.c_void_p]
     L.mgs_map_append.restype = C.c_int32
     L.mgs_map_append.argtypes = [C.POINTER(MapAppendArgs), C.c_void_p]
+    L.mgs_ssim_loss_partial_count.restype = C.c_int32
+    L.mgs_ssim_loss_partial_count.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mgs_ssim_loss.restype = C.c_int32
+    L.mgs_ssim_loss.argtypes = [C.POINTER(SsimLossArgs), C.c_void_p]
+    L.mgs_refine_view_iteration.restype = C.c_int32
+    L.mgs_refine_view_iteration.argtypes = [C.POINTER(RefineViewArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")
@@ -301,7 +320,7 @@ def struct_mirrors():
     return [RasterShape, WorkspaceSizes, ForwardArgs, BackwardArgs, PoseAdamArgs, MappingLossArgs,
             LMStepArgs, TrackingLossArgs, TrackingIterArgs, SketchResidualArgs, TrackingSOArgs,
             AdamGroup, MapPlanArgs, GatherTensor, MapGatherArgs, MapAccumArgs, MapActivateArgs,
-            MappingViewArgs, MapFinishArgs, MapAppendArgs]
+            MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs]
 
 
 def check(status: int, what: str) -> None:

@@ -32,6 +32,7 @@ int launch_forward_blend(const KP& P, hipStream_t st);
 int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_reduce, const SketchFuse* fuse);
 int launch_knn(const float* pts, int n, float* out, void* scratch, hipStream_t st);
 int launch_visibility(const int* n_touched, unsigned char* vis, int n, hipStream_t st);
+int launch_radii_fold(const int* radii, float* max_radii, int n, hipStream_t st);
 uint64_t knn_scratch_bytes(int n);
 }  // namespace mgs
 
@@ -132,6 +133,8 @@ int32_t mgs_struct_size(int32_t which) {
     case 17: return (int32_t)sizeof(mgs_mapping_view_args);
     case 18: return (int32_t)sizeof(mgs_map_finish_args);
     case 19: return (int32_t)sizeof(mgs_map_append_args);
+    case 20: return (int32_t)sizeof(mgs_ssim_loss_args);
+    case 21: return (int32_t)sizeof(mgs_refine_view_args);
     default: return -1;
   }
 }
@@ -316,19 +319,46 @@ int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream)
   return mgs_pose_adam_step(&A, stream);
 }
 
+}  // extern "C"
+
+namespace {
+// The render and the mapping-mode backward of one view, shared by mgs_mapping_view_iteration and
+// mgs_refine_view_iteration (the objective between them differs).
+static int32_t map_view_render(const mgs_forward_args& fwd, const float* T, int32_t camera_matrices_valid, void* stream) {
+  int32_t rc = MGS_OK;
+  if (!camera_matrices_valid) {
+    rc = mgs_camera_from_pose(T, fwd.projmatrix_raw, const_cast<float*>(fwd.viewmatrix), const_cast<float*>(fwd.projmatrix),
+                              stream);
+    if (rc != MGS_OK) return rc;
+  }
+  if ((rc = mgs_raster_forward_project(&fwd, stream)) != MGS_OK) return rc;
+  return mgs_raster_forward_blend(&fwd, stream);
+}
+
+static int32_t map_view_backward(const mgs_forward_args& fwd, const float* grad_image, const float* grad_depth, void* bwd,
+                                 float* grad_tau, const mgs_map_accum_args* accum, const float** tau_partials,
+                                 int32_t* npre, void* stream) {
+  mgs_backward_args B;
+  memset(&B, 0, sizeof(B));
+  B.fwd = fwd;
+  B.grad_color = grad_image;
+  B.grad_depth = grad_depth;
+  B.bwd = bwd;
+  B.grad_tau = grad_tau;
+  B.map_accum = accum;
+  return raster_backward_impl(&B, stream, true, tau_partials, npre);
+}
+}  // namespace
+
+extern "C" {
+
 int32_t mgs_mapping_view_iteration(const mgs_mapping_view_args* args, void* stream) {
   if (!args || !args->adam.T || !args->fwd.viewmatrix || !args->fwd.projmatrix || args->fwd.shape.pair_capacity < 1)
     return MGS_ERR_BAD_ARGUMENT;
   if (!args->forward_only && (!args->bwd || !args->grad_image || !args->grad_tau || !args->loss.partial || !args->loss.gt))
     return MGS_ERR_BAD_ARGUMENT;
   int32_t rc = MGS_OK;
-  if (!args->camera_matrices_valid) {
-    rc = mgs_camera_from_pose(args->adam.T, args->fwd.projmatrix_raw, const_cast<float*>(args->fwd.viewmatrix),
-                              const_cast<float*>(args->fwd.projmatrix), stream);
-    if (rc != MGS_OK) return rc;
-  }
-  if ((rc = mgs_raster_forward_project(&args->fwd, stream)) != MGS_OK) return rc;
-  if ((rc = mgs_raster_forward_blend(&args->fwd, stream)) != MGS_OK) return rc;
+  if ((rc = map_view_render(args->fwd, args->adam.T, args->camera_matrices_valid, stream)) != MGS_OK) return rc;
   if (args->forward_only) {
     if (args->accum.visibility) {
       return launch_visibility((const int*)args->fwd.n_touched, args->accum.visibility,
@@ -344,17 +374,11 @@ int32_t mgs_mapping_view_iteration(const mgs_mapping_view_args* args, void* stre
   int32_t nblk = 0;
   if ((rc = mgs_mapping_loss_fused(&L, &nblk, stream)) != MGS_OK) return rc;
   // full backward in mapping mode
-  mgs_backward_args B;
-  memset(&B, 0, sizeof(B));
-  B.fwd = args->fwd;
-  B.grad_color = args->grad_image;
-  B.grad_depth = L.grad_depth;
-  B.bwd = args->bwd;
-  B.grad_tau = args->grad_tau;
-  B.map_accum = &args->accum;
   const float* tau_partials = nullptr;
   int32_t npre = 0;
-  if ((rc = raster_backward_impl(&B, stream, true, &tau_partials, &npre)) != MGS_OK) return rc;
+  if ((rc = map_view_backward(args->fwd, args->grad_image, L.grad_depth, args->bwd, args->grad_tau, &args->accum,
+                              &tau_partials, &npre, stream)) != MGS_OK)
+    return rc;
   // this view's pose / exposure optimiser step (+ update_pose), loss value
   mgs_pose_adam_args A = args->adam;
   A.grad_trans = nullptr; A.grad_rot = nullptr; A.grad_a = nullptr; A.grad_b = nullptr;
@@ -369,6 +393,28 @@ int32_t mgs_mapping_view_iteration(const mgs_mapping_view_args* args, void* stre
   A.viewmatrix_out = const_cast<float*>(args->fwd.viewmatrix);
   A.projmatrix_out = const_cast<float*>(args->fwd.projmatrix);
   return mgs_pose_adam_step(&A, stream);
+}
+
+int32_t mgs_refine_view_iteration(const mgs_refine_view_args* args, void* stream) {
+  if (!args || !args->T || !args->fwd.viewmatrix || !args->fwd.projmatrix || !args->fwd.out_color || !args->fwd.radii ||
+      args->fwd.shape.pair_capacity < 1 || !args->bwd || !args->grad_image || !args->grad_tau || !args->max_radii2D ||
+      !args->loss.gt || !args->loss.partial || !args->loss.loss)
+    return MGS_ERR_BAD_ARGUMENT;
+  int32_t rc = MGS_OK;
+  if ((rc = map_view_render(args->fwd, args->T, args->camera_matrices_valid, stream)) != MGS_OK) return rc;
+  // loss = (1 - lambda) l1 + lambda (1 - ssim) on the render as it is: no exposure, no mask (slam_backend.py:355-358)
+  mgs_ssim_loss_args L = args->loss;
+  L.channels = 3; L.height = args->fwd.shape.height; L.width = args->fwd.shape.width;
+  L.image = args->fwd.out_color; L.grad_image = args->grad_image; L.grad_out = nullptr;
+  if ((rc = mgs_ssim_loss(&L, stream)) != MGS_OK) return rc;
+  // backward in mapping mode: this view's gradients alone, no statistics (no add_densification_stats in :341-367)
+  mgs_map_accum_args M = args->accum;
+  M.accumulate = 0; M.add_regulariser = 0;
+  M.gradnorm_inc = nullptr; M.denom_inc = nullptr; M.radii_max = nullptr; M.visibility = nullptr;
+  if ((rc = map_view_backward(args->fwd, args->grad_image, nullptr, args->bwd, args->grad_tau, &M, nullptr, nullptr,
+                              stream)) != MGS_OK)
+    return rc;
+  return launch_radii_fold(args->fwd.radii, args->max_radii2D, args->fwd.shape.num_gaussians, (hipStream_t)stream);
 }
 
 int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, void* stream) {

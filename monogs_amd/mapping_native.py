@@ -49,7 +49,7 @@ DEFAULT_MAP_CONFIG = {
         "pose_window": 3, "prune_mode": "slam",
         "lr": {"cam_rot_delta": 0.003, "cam_trans_delta": 0.001, "exposure_a": 0.02, "exposure_b": 0.02},
     },
-    "opt_params": {"densify_grad_threshold": 0.0002, "densify_from_iter": 500},
+    "opt_params": {"densify_grad_threshold": 0.0002, "densify_from_iter": 500, "lambda_dssim": 0.2},
 }
 
 
@@ -246,15 +246,11 @@ class NativeMapper:
             st.step = 0
 
     # ---- one view ----------------------------------------------------------------------------------
-    def _view_args(self, kf_idx, cam_idx, *, accumulate, add_reg, initialization=False, forward_only=False,
-                   in_window=True, stats=True, lane=None):
-        vp, st, g = self.viewpoints[kf_idx], self.states[kf_idx], self.gaussians
-        tr = self.cfg["Training"]
-        ln = self.lanes[0] if lane is None else lane
+    def _fill_forward(self, f, vp, st, ln):
+        """The rasteriser forward of one view into lane `ln` (workspaces sized here); returns (W, H)."""
+        g = self.gaussians
         W, H = int(vp.image_width), int(vp.image_height)
         self._ensure_workspaces(ln, W, H, int(g.active_sh_degree))
-        a = _cabi.MappingViewArgs()
-        f = a.fwd
         f.shape = _cabi.RasterShape(self._N, W, H, int(g.active_sh_degree), self.K, self.capacity,
                                     math.tan(0.5 * vp.FoVx), math.tan(0.5 * vp.FoVy), 1.0)
         f.means3D, f.scales, f.rotations = g._xyz.data_ptr(), self.scales.data_ptr(), self.rots.data_ptr()
@@ -267,6 +263,15 @@ class NativeMapper:
         f.radii, f.n_touched = ln.radii.data_ptr(), ln.n_touched.data_ptr()
         f.pair_count_out, f.pair_count_max = ln.host_D.data_ptr(), ln.d_max.data_ptr()
         f.big_tile_pass = -1 if 0 < int(ln.host_D[1]) <= 900 else 0
+        return W, H
+
+    def _view_args(self, kf_idx, cam_idx, *, accumulate, add_reg, initialization=False, forward_only=False,
+                   in_window=True, stats=True, lane=None):
+        vp, st, g = self.viewpoints[kf_idx], self.states[kf_idx], self.gaussians
+        tr = self.cfg["Training"]
+        ln = self.lanes[0] if lane is None else lane
+        a = _cabi.MappingViewArgs()
+        W, H = self._fill_forward(a.fwd, vp, st, ln)
         a.bwd, a.grad_image, a.grad_tau = ln.bwd.data_ptr(), ln.grad_image.data_ptr(), ln.grad_tau.data_ptr()
         a.grad_depth = ln.grad_depth.data_ptr()
         # objective (utils/slam_utils.py:224-253)
@@ -345,10 +350,9 @@ class NativeMapper:
         self.capacity = max(self.capacity, 1024, (int(D * self.capacity_margin) + 1023) // 1024 * 1024)
         self._need_probe = False
 
-    def _run_view(self, kf_idx, cam_idx, lane=None, **kw):
+    def _grow_capacity(self, kf_idx):
         if self._need_probe:
             self._probe_capacity(kf_idx)
-        ln = self.lanes[0] if lane is None else lane
         # D of an earlier view lands in pinned host memory without a sync: grow BEFORE it overflows
         seen = max(int(l.host_D[0].item()) for l in self.lanes)
         if seen > 0.9 * self.capacity:
@@ -356,6 +360,10 @@ class NativeMapper:
                 torch.cuda.synchronize(self.dev)        # workspaces of other streams are about to be replaced
             self.capacity = (int(seen * self.capacity_margin) + 1023) // 1024 * 1024
             self.overflow_regrows += 1
+
+    def _run_view(self, kf_idx, cam_idx, lane=None, **kw):
+        self._grow_capacity(kf_idx)
+        ln = self.lanes[0] if lane is None else lane
         a, st = self._view_args(kf_idx, cam_idx, lane=ln, **kw)
         _cabi.check(_cabi.lib().mgs_mapping_view_iteration(C.byref(a), ln.stream_ptr()), "mgs_mapping_view_iteration")
         st.matrices_fresh = not kw.get("forward_only", False)   # the Adam kernel wrote the updated matrices
@@ -610,3 +618,69 @@ class NativeMapper:
                 self._step_gaussians(skip=("_opacity",) if reset else ())
         self.last_loss = self.loss_accum.clone()
         return self.occ_aware_visibility.get(kf_idx)
+
+    # ---- color_refinement (:335-368) ----------------------------------------------------------------------------
+    def _run_refine_view(self, kf_idx, lam, loss_out):
+        """One mgs_refine_view_iteration of keyframe kf_idx on lane 0: render, colour-refinement objective, backward
+        into the flat buffer's gradient sections (overwritten), max_radii2D fold; the loss lands in loss_out[0]."""
+        self._grow_capacity(kf_idx)
+        vp, st, g = self.viewpoints[kf_idx], self.states[kf_idx], self.gaussians
+        ln = self.lanes[0]
+        a = _cabi.RefineViewArgs()
+        W, H = self._fill_forward(a.fwd, vp, st, ln)
+        a.bwd, a.grad_image, a.grad_tau = ln.bwd.data_ptr(), ln.grad_image.data_ptr(), ln.grad_tau.data_ptr()
+        assert vp.T.is_contiguous() and vp.T.dtype == torch.float32 and vp.T.device == self.dev
+        if vp.T.data_ptr() != st.T_ptr:
+            st.matrices_fresh, st.T_ptr = False, vp.T.data_ptr()
+        a.T = vp.T.data_ptr()
+        count = int(_cabi.lib().mgs_ssim_loss_partial_count(3, H, W))
+        if getattr(ln, "ssim_partial", None) is None or ln.ssim_partial.numel() != count:
+            ln.ssim_partial = torch.zeros(count, device=self.dev)     # the ticket behind it: zero once, kept by the kernel
+        L = a.loss
+        L.w_l1, L.w_ssim = 1.0 - lam, lam
+        L.gt, L.partial, L.loss = st.gt.data_ptr(), ln.ssim_partial.data_ptr(), loss_out.data_ptr()
+        M = a.accum
+        M.scale_dims, M.raw_rotations = self.sd, g._rotation.data_ptr()
+        ptr = lambda name: self._section(name, ln).data_ptr()
+        M.grad_xyz, M.grad_features_dc, M.grad_opacity = ptr("xyz"), ptr("f_dc"), ptr("opacity")
+        M.grad_features_rest = ptr("f_rest") if self.K > 1 else None
+        M.grad_scaling, M.grad_rotation = ptr("scaling"), ptr("rotation")
+        a.max_radii2D = g.max_radii2D.data_ptr()
+        a.camera_matrices_valid = 1 if st.matrices_fresh else 0
+        _cabi.check(_cabi.lib().mgs_refine_view_iteration(C.byref(a), ln.stream_ptr()), "mgs_refine_view_iteration")
+        st.matrices_fresh = True         # T does not move during refinement: the matrices just formed stay valid
+        ln.keep = a
+
+    def color_refinement(self, iterations: int = 26000, lambda_dssim: Optional[float] = None):
+        """BackEnd.color_refinement (slam_backend.py:335-368): `iterations` single-view iterations over every
+        keyframe the mapper holds, each one mgs_refine_view_iteration (render without exposure or mask,
+        (1 - lambda) l1 + lambda (1 - ssim) and its gradient in one launch, backward, max_radii2D fold) followed
+        by the Gaussians' optimiser step and update_learning_rate(it), it = 1 .. iterations - the refinement's
+        own counter.  The views are drawn uniformly from list(self.viewpoints) with self.rng, all draws made up
+        front: torch.randint(len(views), (iterations,), generator=self.rng).
+        iteration_count, xyz_gradient_accum, denom, every camera's T and exposure and the keyframe optimiser
+        state are left as they are.  Per-iteration losses are kept on the device in self.refine_losses;
+        last_loss is the last of them.  No host sync beyond what map() does (the pinned pair count read for
+        the capacity regrow).
+        Keyframe-parallel (world > 1): every rank runs the same iterations on its replica of the map with no
+        collective - the draws come from the identically seeded generator and the forward, the loss and the
+        backward are deterministic, so the replicas stay identical."""
+        lam = float(self.cfg["opt_params"]["lambda_dssim"] if lambda_dssim is None else lambda_dssim)
+        keys = list(self.viewpoints)
+        if not keys or iterations < 1:
+            return
+        g = self.gaussians
+        draws = torch.randint(len(keys), (iterations,), generator=self.rng).tolist()
+        for st in self.states.values():       # T may have been moved from outside since the last call
+            st.matrices_fresh = False
+        losses = torch.zeros(iterations, device=self.dev)
+        for it, d in enumerate(draws, start=1):
+            self._ensure_model_buffers()
+            if g.max_radii2D.shape[0] != self._N:
+                raise RuntimeError("gaussians.max_radii2D does not match the number of Gaussians")
+            self._activate()
+            self._run_refine_view(keys[d], lam, losses[it - 1:it])
+            self._step_gaussians()
+            g.update_learning_rate(it)
+        self.refine_losses = losses
+        self.last_loss = losses[-1:].clone()

@@ -5,6 +5,7 @@ densification policy, queues and GUI are out of scope):
   * tracking, first order   /root/reference utils/slam_frontend.py:455-630
   * tracking, second order  utils/slam_frontend.py:269-338 (sketch args), :632-710 (LM step)
   * mapping                 utils/slam_backend.py:171-332
+  * colour refinement       utils/slam_backend.py:335-368
 Hyper-parameters default to configs/mono/tum/base_config.yaml:245-290.
 """
 from __future__ import annotations
@@ -414,3 +415,31 @@ def mapping_step(window: List[ViewCamera], gaussians, gaussian_optimizer, keyfra
                 update_pose(vp)
     loss = loss.detach() if torch.is_tensor(loss) else torch.zeros(())
     return loss, grad_norm, denom, max_radii
+
+
+def color_refinement_step(viewpoint, gaussians, background, lambda_dssim, iteration, pipe=Pipe, render_fn=None,
+                          loss_fn=None):
+    """One iteration of BackEnd.color_refinement (slam_backend.py:341-367) for the view the caller drew: render
+    (no exposure, no mask, depth unused), (1 - lambda) l1 + lambda (1 - ssim), backward, the max_radii2D fold,
+    the Gaussians' optimiser step, zero_grad and update_learning_rate(iteration) - `iteration` is the
+    refinement's own counter (1, 2, ...).  No densification statistics, no camera or exposure step.
+    By default the loss is the reference's own arithmetic (eval_metrics.ssim, pinned to loss_utils.ssim, and
+    the plain L1); `loss_fn(image, gt, lambda_dssim)` swaps in another (tracking_fused.color_refinement_loss).
+    Returns the detached loss."""
+    from .eval_metrics import ssim
+    render_fn = render if render_fn is None else render_fn
+    pkg = render_fn(viewpoint, gaussians, pipe, background)
+    image, visibility_filter, radii = pkg["render"], pkg["visibility_filter"], pkg["radii"]
+    gt_image = viewpoint.original_image
+    if loss_fn is None:
+        loss = (1.0 - lambda_dssim) * torch.abs(image - gt_image).mean() + lambda_dssim * (1.0 - ssim(image, gt_image))
+    else:
+        loss = loss_fn(image, gt_image, lambda_dssim)
+    loss.backward()
+    with torch.no_grad():
+        gaussians.max_radii2D[visibility_filter] = torch.max(gaussians.max_radii2D[visibility_filter],
+                                                             radii[visibility_filter])
+        gaussians.optimizer.step()
+        gaussians.optimizer.zero_grad(set_to_none=True)
+        gaussians.update_learning_rate(iteration)
+    return loss.detach()

@@ -141,11 +141,12 @@ def lm_solve_step(SJ: torch.Tensor, Sf: torch.Tensor, lambda_: float, viewpoint=
 _loss_scratch: dict = {}
 
 
-def _zeroed_partials(dev, count):
+def _zeroed_partials(dev, count, kind="mapping"):
     """Per-(device, stream) scratch for the loss kernels' block partials, zeroed ONCE: the forward's
     last-workgroup ticket lives behind the partials and every call restores it to zero, so calls
-    enqueued in order on one stream can share the buffer."""
-    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, count)
+    enqueued in order on one stream can share the buffer (`kind` keeps kernels with different
+    layouts - and tickets at different offsets - apart)."""
+    key = (dev.index, torch.cuda.current_stream(dev).cuda_stream, count, kind)
     buf = _loss_scratch.get(key)
     if buf is None:
         if len(_loss_scratch) > 64:
@@ -270,3 +271,60 @@ def l1_image_depth_loss_backward(image, depth, gt_image, gt_depth, w_depth=0.05,
             if p.requires_grad:
                 p.grad = g.reshape(p.shape).clone() if p.grad is None else p.grad + g.reshape(p.shape)
     return out[0]
+
+
+class _ColorRefinementLoss(torch.autograd.Function):
+    """Value and d/d image in the forward (one launch); the backward only scales the stored gradient by the
+    upstream scalar on the device - no launch of ours and no host sync."""
+
+    @staticmethod
+    def forward(ctx, image, gt, w_l1, w_ssim):
+        dev = image.device
+        if dev.type != "cuda" or gt.device != dev:
+            raise RuntimeError("fused colour-refinement loss runs on the GPU only; use eval_metrics.ssim on CPU")
+        if image.dim() != 3 or image.shape != gt.shape:
+            raise ValueError(f"image and gt must both be [C,H,W] of one shape, got {tuple(image.shape)} and {tuple(gt.shape)}")
+        lib = _cabi.lib()
+        image_c = image.detach().float().contiguous()
+        gt_c = gt.detach().float().contiguous()
+        C_, H, W = (int(v) for v in image_c.shape)
+        count = int(lib.mgs_ssim_loss_partial_count(C_, H, W))
+        if count < 0:
+            raise ValueError(f"image size {tuple(image_c.shape)} is not supported by mgs_ssim_loss")
+        partial = _zeroed_partials(dev, count, kind="ssim")
+        loss = torch.empty((), dtype=torch.float32, device=dev)
+        terms = torch.empty(2, dtype=torch.float32, device=dev)      # l1, ssim
+        want_grad = ctx.needs_input_grad[0]
+        g_img = torch.empty_like(image_c) if want_grad else None
+        a = _cabi.SsimLossArgs()
+        a.channels, a.height, a.width = C_, H, W
+        a.w_l1, a.w_ssim = float(w_l1), float(w_ssim)
+        a.image, a.gt = image_c.data_ptr(), gt_c.data_ptr()
+        a.grad_image = None if g_img is None else g_img.data_ptr()
+        a.partial = partial.data_ptr()
+        a.loss, a.l1, a.ssim = loss.data_ptr(), terms.data_ptr(), terms[1:].data_ptr()
+        _cabi.check(lib.mgs_ssim_loss(C.byref(a), _stream(dev)), "mgs_ssim_loss")
+        ctx.save_for_backward(g_img)
+        ctx.mark_non_differentiable(terms)
+        ctx.image_dtype = image.dtype
+        return loss, terms
+
+    @staticmethod
+    def backward(ctx, grad_out, _grad_terms):
+        (g_img,) = ctx.saved_tensors
+        if grad_out is None or g_img is None:
+            return None, None, None, None
+        return (g_img * grad_out.float()).to(ctx.image_dtype), None, None, None
+
+
+def color_refinement_loss(image, gt, lambda_dssim=0.2, return_terms=False):
+    """(1 - lambda) l1_loss(image, gt) + lambda (1 - ssim(image, gt)) of BackEnd.color_refinement
+    (utils/slam_backend.py:355-358; loss_utils.py:21-22,63-101), differentiable w.r.t. `image` ([C,H,W]).  One
+    HIP launch (mgs_ssim_loss) forms the value and the gradient.  With return_terms it returns
+    (loss, l1, ssim), the last two detached device scalars for logging."""
+    if torch.is_tensor(gt) and gt.requires_grad:
+        raise ValueError("color_refinement_loss differentiates w.r.t. image only: gt must not require grad")
+    loss, terms = _ColorRefinementLoss.apply(image, gt, 1.0 - float(lambda_dssim), float(lambda_dssim))
+    if return_terms:
+        return loss, terms[0], terms[1]
+    return loss
