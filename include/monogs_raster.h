@@ -204,7 +204,7 @@ int32_t mgs_abi_version(void);
  * 11 = mgs_adam_group, 12 = mgs_map_plan_args, 13 = mgs_gather_tensor, 14 = mgs_map_gather_args,
  * 15 = mgs_map_accum_args, 16 = mgs_map_activate_args, 17 = mgs_mapping_view_args,
  * 18 = mgs_map_finish_args, 19 = mgs_map_append_args, 20 = mgs_ssim_loss_args,
- * 21 = mgs_refine_view_args);
+ * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args);
  * -1 for an unknown index.  Lets a foreign-language binding verify its struct mirrors. */
 int32_t mgs_struct_size(int32_t which);
 const char* mgs_status_string(int32_t status);
@@ -571,6 +571,47 @@ typedef struct mgs_tracking_so_args {
 } mgs_tracking_so_args;
 
 int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, void* stream);
+
+/* ---- RGB-D tracking: the depth residual stacked onto the tracking objective -----------------
+ * The reference's unfinished get_loss_tracking_rgbd_per_pixel (utils/slam_utils.py:208-221) with its two terms
+ * STACKED along the channel axis instead of added, so that the first-order norm, the best-iterate L1 and the
+ * second-order bucket sums all run unchanged on the four rows:
+ *   r_c = w_rgb * opacity * mask * ((|a| + eps) image_c + b - gt_c)            c = 0..2 (the monocular rows)
+ *   dm  = (gt_depth > depth_threshold) && (opacity > opacity_threshold)        (rendered opacity, not differentiated)
+ *   r_d = w_depth * (depth * dm - gt_depth * dm)
+ * w_rgb = alpha (config Training.alpha, 0.95 by default), w_depth = 1 - alpha.  Huber acts on the weighted rows.
+ * The depth row does not depend on the exposure.  Every *_rgbd entry point takes the monocular argument block
+ * unchanged plus this one; grad_depth receives d/d depth where the monocular entry writes d/d image. */
+typedef struct mgs_tracking_depth_args {
+  const float* depth;          /* [1,H,W] rendered depth (the iteration entry points use fwd.out_depth instead) */
+  const float* gt_depth;       /* [1,H,W] sensor depth */
+  float* grad_depth;           /* [1,H,W] out (scratch of the iteration entry points) */
+  float w_rgb;                 /* alpha */
+  float w_depth;               /* 1 - alpha */
+  float depth_threshold;       /* 0.01 (slam_utils.py:214) */
+  float opacity_threshold;     /* 0.95 (slam_utils.py:215) */
+} mgs_tracking_depth_args;
+
+/* mgs_tracking_iteration with the stacked objective: the forward blend's epilogue adds the depth row (grad_depth
+ * written there), the pose-only backward consumes grad_depth.  Any p other than 1 and 2 takes
+ * mgs_tracking_loss_rgbd_fused (onepass form) between the forward and the backward (loss.partial needed). */
+int32_t mgs_tracking_iteration_rgbd(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* depth,
+                                    void* stream);
+/* mgs_tracking_iteration_second_order with the stacked objective: the sketched residual pass adds Huber(r_d) to the
+ * pixel's bucket, the Jacobian-only sketch backward consumes grad_depth. */
+int32_t mgs_tracking_iteration_second_order_rgbd(const mgs_tracking_so_args* args, const mgs_tracking_depth_args* depth,
+                                                 void* stream);
+/* Stacked objective, value and gradient: ONE pass writes the block sums of mgs_tracking_loss_onepass (partial =
+ * [n] sum |h|^p | [n] d/da | [n] d/db | [n] sum |r| over the four rows, n = *num_blocks_out) and the UN-normalised
+ * gradients (as if loss^(1-p) were 1) into grad_image and depth->grad_depth.  With scalars != NULL a second launch
+ * sums the partials: scalars[0] = loss, scalars[1] = loss^(1-p) (the factor the gradients still need), and
+ * grad_a / grad_b (when not NULL) = d loss / d a, d loss / d b including that factor.  `partial` holds
+ * mgs_tracking_loss_partial_count floats. */
+int32_t mgs_tracking_loss_rgbd_fused(const mgs_tracking_loss_args* args, const mgs_tracking_depth_args* depth,
+                                     int32_t* num_blocks_out, void* stream);
+/* mgs_sketch_residual with the depth row: hs += Huber(r_d) into the pixel's bucket, l1 += |r_d|,
+ * grad_depth = weight * Huber'(r_d) * w_depth * dm. */
+int32_t mgs_sketch_residual_rgbd(const mgs_sketch_residual_args* args, const mgs_tracking_depth_args* depth, void* stream);
 
 /* ---- map maintenance on the device ---------------------------------- */
 

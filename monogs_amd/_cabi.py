@@ -27,6 +27,8 @@ EXPORTS = (
     "mgs_tracking_iteration_second_order", "mgs_map_activate", "mgs_mapping_loss_partial_count",
     "mgs_mapping_loss_fused", "mgs_mapping_view_iteration", "mgs_map_finish_iteration", "mgs_map_append",
     "mgs_ssim_loss_partial_count", "mgs_ssim_loss", "mgs_refine_view_iteration",
+    "mgs_tracking_iteration_rgbd", "mgs_tracking_iteration_second_order_rgbd", "mgs_tracking_loss_rgbd_fused",
+    "mgs_sketch_residual_rgbd",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -203,6 +205,11 @@ class RefineViewArgs(C.Structure):
                 ("camera_matrices_valid", C.c_int32), ("reserved0", C.c_int32)]
 
 
+class TrackingDepthArgs(C.Structure):
+    _fields_ = ([(n, _fp) for n in ("depth", "gt_depth", "grad_depth")]
+                + [(n, C.c_float) for n in ("w_rgb", "w_depth", "depth_threshold", "opacity_threshold")])
+
+
 _lib = None
 
 
@@ -308,6 +315,15 @@ def lib():
     L.mgs_ssim_loss.argtypes = [C.POINTER(SsimLossArgs), C.c_void_p]
     L.mgs_refine_view_iteration.restype = C.c_int32
     L.mgs_refine_view_iteration.argtypes = [C.POINTER(RefineViewArgs), C.c_void_p]
+    _dp = C.POINTER(TrackingDepthArgs)
+    L.mgs_tracking_iteration_rgbd.restype = C.c_int32
+    L.mgs_tracking_iteration_rgbd.argtypes = [C.POINTER(TrackingIterArgs), _dp, C.c_void_p]
+    L.mgs_tracking_iteration_second_order_rgbd.restype = C.c_int32
+    L.mgs_tracking_iteration_second_order_rgbd.argtypes = [C.POINTER(TrackingSOArgs), _dp, C.c_void_p]
+    L.mgs_tracking_loss_rgbd_fused.restype = C.c_int32
+    L.mgs_tracking_loss_rgbd_fused.argtypes = [C.POINTER(TrackingLossArgs), _dp, C.POINTER(C.c_int32), C.c_void_p]
+    L.mgs_sketch_residual_rgbd.restype = C.c_int32
+    L.mgs_sketch_residual_rgbd.argtypes = [C.POINTER(SketchResidualArgs), _dp, C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")
@@ -320,7 +336,7 @@ def struct_mirrors():
     return [RasterShape, WorkspaceSizes, ForwardArgs, BackwardArgs, PoseAdamArgs, MappingLossArgs,
             LMStepArgs, TrackingLossArgs, TrackingIterArgs, SketchResidualArgs, TrackingSOArgs,
             AdamGroup, MapPlanArgs, GatherTensor, MapGatherArgs, MapAccumArgs, MapActivateArgs,
-            MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs]
+            MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs, TrackingDepthArgs]
 
 
 def check(status: int, what: str) -> None:

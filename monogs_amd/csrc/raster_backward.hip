@@ -583,6 +583,15 @@ __global__ __launch_bounds__(kPreBlock) void k_sketch_prep_residual(KP P, KB B, 
   else sketch_prep_gaussian(P, B, ((int)blockIdx.x - res_blocks) * kPreBlock + threadIdx.x);
 }
 
+// the same with the RGB-D residual (depth row stacked under the colour rows)
+__global__ __launch_bounds__(kPreBlock) void k_sketch_prep_residual_rgbd(KP P, KB B, mgs_sketch_residual_args A, SketchKeys K,
+                                                                         int res_blocks, mgs_tracking_depth_args D) {
+  extern __shared__ float s_acc[];   // residual role: [d][3]
+  __shared__ float s_red[kSketchThreads / 64];
+  if ((int)blockIdx.x < res_blocks) sketch_residual_block<true>(A, K, s_acc, s_red, blockIdx.x, res_blocks, &D);
+  else sketch_prep_gaussian(P, B, ((int)blockIdx.x - res_blocks) * kPreBlock + threadIdx.x);
+}
+
 constexpr int kBucketBlocks = 256;      // persistent workgroups (one per CU), four tiles in hand each (64 / 128 / 256 / 512
                                         // measured: 56.7 / 38.5 / 32.7 / 39.9 us)
 constexpr int kBucketThreads = 1024;
@@ -961,8 +970,12 @@ int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_redu
       if (smem > 48 * 1024) return MGS_ERR_UNSUPPORTED;
       const long long want = (A.num_pixels + kSketchThreads - 1) / kSketchThreads;
       const int res_blocks = (int)(want < kSketchBlocks ? want : kSketchBlocks);
-      launch_smem("sketch_prep_residual", k_sketch_prep_residual, dim3(res_blocks + (fuse->skip_prep ? 0 : prep_blocks)),
-                  dim3(kPreBlock), smem, st, P, B, A, fuse->keys, res_blocks);
+      if (fuse->depth)
+        launch_smem("sketch_prep_residual_rgbd", k_sketch_prep_residual_rgbd, dim3(res_blocks + (fuse->skip_prep ? 0 : prep_blocks)),
+                    dim3(kPreBlock), smem, st, P, B, A, fuse->keys, res_blocks, *fuse->depth);
+      else
+        launch_smem("sketch_prep_residual", k_sketch_prep_residual, dim3(res_blocks + (fuse->skip_prep ? 0 : prep_blocks)),
+                    dim3(kPreBlock), smem, st, P, B, A, fuse->keys, res_blocks);
     } else if (!(fuse && fuse->skip_prep)) {
       launch("sketch_prep", k_sketch_prep, dim3(prep_blocks), dim3(kPreBlock), st, P, B);
     }

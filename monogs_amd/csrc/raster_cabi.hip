@@ -28,7 +28,7 @@ void profile_push(const char* name, hipEvent_t a, hipEvent_t b) {
 
 namespace mgs {
 int launch_forward_project(const KP& P, hipStream_t st);
-int launch_forward_blend(const KP& P, hipStream_t st);
+int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD = nullptr);
 int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_reduce, const SketchFuse* fuse);
 int launch_knn(const float* pts, int n, float* out, void* scratch, hipStream_t st);
 int launch_visibility(const int* n_touched, unsigned char* vis, int n, hipStream_t st);
@@ -135,6 +135,7 @@ int32_t mgs_struct_size(int32_t which) {
     case 19: return (int32_t)sizeof(mgs_map_append_args);
     case 20: return (int32_t)sizeof(mgs_ssim_loss_args);
     case 21: return (int32_t)sizeof(mgs_refine_view_args);
+    case 22: return (int32_t)sizeof(mgs_tracking_depth_args);
     default: return -1;
   }
 }
@@ -251,7 +252,11 @@ int32_t mgs_raster_backward(const mgs_backward_args* args, void* stream) {
   return raster_backward_impl(args, stream, false, nullptr, nullptr);
 }
 
-int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream) {
+}  // extern "C"
+
+// D != nullptr: the RGB-D objective (include/monogs_raster.h: mgs_tracking_depth_args); the launch sequence is the
+// monocular one with the depth row in the objective and grad_depth handed to the backward.
+static int32_t tracking_iteration_impl(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* D, void* stream) {
   if (!args || !args->bwd || !args->grad_image || !args->grad_tau || !args->grad_exposure ||
       !args->one || !args->adam.T || !args->fwd.viewmatrix || !args->fwd.projmatrix)
     return MGS_ERR_BAD_ARGUMENT;
@@ -285,7 +290,13 @@ int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream)
     P.obj.exposure_eps = L.exposure_eps; P.obj.huber_delta = L.huber_delta;
     P.obj.gt = L.gt; P.obj.mask = L.mask; P.obj.exposure_a = L.exposure_a; P.obj.exposure_b = L.exposure_b;
     P.obj.grad_image = args->grad_image; P.obj.partial = obj_partial;
-    if ((rc = launch_forward_blend(P, (hipStream_t)stream)) != MGS_OK) return rc;
+    KObjDepth PD{};
+    if (D) {
+      PD.gt_depth = D->gt_depth; PD.grad_depth = D->grad_depth;
+      PD.w_rgb = D->w_rgb; PD.w_depth = D->w_depth;
+      PD.depth_thr = D->depth_threshold; PD.opa_thr = D->opacity_threshold;
+    }
+    if ((rc = launch_forward_blend(P, (hipStream_t)stream, D ? &PD : nullptr)) != MGS_OK) return rc;
     L.partial = obj_partial;
   } else {
     // any other p >= 1 (powf per sample): the plain forward blend, then the one-pass loss kernel
@@ -294,12 +305,21 @@ int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream)
     if ((rc = launch_forward_blend(P, (hipStream_t)stream)) != MGS_OK) return rc;
     L.image = args->fwd.out_color; L.opacity = args->fwd.out_opacity; L.grad_image = args->grad_image;
     L.num_pixels = (int64_t)P.W * P.H;
-    if ((rc = mgs_tracking_loss_onepass(&L, &nblk, stream)) != MGS_OK) return rc;
+    if (D) {
+      mgs_tracking_depth_args Dd = *D;
+      Dd.depth = args->fwd.out_depth;
+      L.scalars = nullptr;                  // onepass form: the Adam kernel finishes the sums
+      if ((rc = mgs_tracking_loss_rgbd_fused(&L, &Dd, &nblk, stream)) != MGS_OK) return rc;
+      L.scalars = args->loss.scalars;
+    } else if ((rc = mgs_tracking_loss_onepass(&L, &nblk, stream)) != MGS_OK) {
+      return rc;
+    }
   }
   mgs_backward_args B;
   memset(&B, 0, sizeof(B));
   B.fwd = args->fwd;
   B.grad_color = args->grad_image;
+  B.grad_depth = D ? D->grad_depth : nullptr;
   B.bwd = args->bwd;
   B.grad_tau = args->grad_tau;
   const float* tau_partials = nullptr;
@@ -317,6 +337,22 @@ int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream)
   A.viewmatrix_out = const_cast<float*>(args->fwd.viewmatrix);
   A.projmatrix_out = const_cast<float*>(args->fwd.projmatrix);
   return mgs_pose_adam_step(&A, stream);
+}
+
+static bool depth_args_ok(const mgs_tracking_depth_args* D) {
+  return D && D->gt_depth && D->grad_depth && D->w_rgb == D->w_rgb && D->w_depth == D->w_depth;
+}
+
+extern "C" {
+
+int32_t mgs_tracking_iteration(const mgs_tracking_iter_args* args, void* stream) {
+  return tracking_iteration_impl(args, nullptr, stream);
+}
+
+int32_t mgs_tracking_iteration_rgbd(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* depth,
+                                    void* stream) {
+  if (!depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
+  return tracking_iteration_impl(args, depth, stream);
 }
 
 }  // extern "C"
@@ -417,7 +453,10 @@ int32_t mgs_refine_view_iteration(const mgs_refine_view_args* args, void* stream
   return launch_radii_fold(args->fwd.radii, args->max_radii2D, args->fwd.shape.num_gaussians, (hipStream_t)stream);
 }
 
-int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, void* stream) {
+}  // extern "C"
+
+static int32_t tracking_iteration_so_impl(const mgs_tracking_so_args* args, const mgs_tracking_depth_args* D,
+                                          void* stream) {
   if (!args) return MGS_ERR_BAD_ARGUMENT;
   const mgs_tracking_iter_args& b = args->base;
   if (!b.bwd || !b.grad_image || !b.grad_tau || !b.adam.T || !b.fwd.viewmatrix || !b.fwd.projmatrix ||
@@ -477,12 +516,16 @@ int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, vo
     // the preparation depends on the camera alone, the later repeats reuse it)
     SketchFuse fuse;
     fuse.residual = &Rr; fuse.skip_prep = r > 0 ? 1 : 0;
+    mgs_tracking_depth_args Dd;
+    if (D) { Dd = *D; Dd.depth = b.fwd.out_depth; }
+    fuse.depth = D ? &Dd : nullptr;
     if (!Rr.gt || !Rr.exposure_a || !Rr.exposure_b || !sketch_keys(HW, args->stack_dim, args->sketch_dim, Rr.assign_key, fuse.keys))
       return fail(MGS_ERR_BAD_ARGUMENT);
     fuse.keys.on = 1;
     mgs_backward_args B;
     memset(&B, 0, sizeof(B));
     B.fwd = b.fwd; B.grad_color = b.grad_image; B.bwd = b.bwd; B.grad_tau = b.grad_tau;
+    B.grad_depth = D ? D->grad_depth : nullptr;
     B.sketch_mode = 1; B.sketch_dim = args->sketch_dim; B.stack_dim = args->stack_dim;
     B.sketch_bucket_flat = args->bucket + (size_t)r * HW; B.grad_sketch_dtau = sj_tau + 6 * (size_t)r * d;
     B.sketch_ws = args->sketch_ws;
@@ -500,6 +543,18 @@ int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, vo
   L.projmatrix_out = const_cast<float*>(b.fwd.projmatrix);
   if ((rc = mgs_lm_solve_step(&L, stream)) != MGS_OK) return fail(rc);
   return MGS_OK;
+}
+
+extern "C" {
+
+int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, void* stream) {
+  return tracking_iteration_so_impl(args, nullptr, stream);
+}
+
+int32_t mgs_tracking_iteration_second_order_rgbd(const mgs_tracking_so_args* args, const mgs_tracking_depth_args* depth,
+                                                 void* stream) {
+  if (!depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
+  return tracking_iteration_so_impl(args, depth, stream);
 }
 
 int32_t mgs_profile_enable(int32_t on) {

@@ -821,9 +821,10 @@ __device__ __forceinline__ void mask_clear_bit(unsigned long long& m, int j) {
 }
 
 
-// OBJ: the tracking objective in the epilogue (raster_kernels.h: KObj).
-template <bool OBJ>
-__global__ __launch_bounds__(64, 6) void k_blend_fwd(KP P) {
+// OBJ: the tracking objective in the epilogue (raster_kernels.h: KObj); DEPTH: its RGB-D form (four rows per pixel,
+// the depth row's arguments in PD).  The kernels are the thin wrappers k_blend_fwd<OBJ> and k_blend_fwd_rgbd below.
+template <bool OBJ, bool DEPTH>
+__device__ __forceinline__ void blend_fwd(const KP& P, const KObjDepth& PD) {
   MGS_STAMP_SCOPE;
   // per staged splat 48 B: (a0, a1, a2, A) (B, C, opacity, -) (r, g, b, depth)
   __shared__ float4 s_rec[kSeg * 3];
@@ -1096,16 +1097,31 @@ __global__ __launch_bounds__(64, 6) void k_blend_fwd(KP P) {
 #pragma unroll
       for (int c = 0; c < 3; c++) {
         float dh;
-        const float r = om * (gain * im[c] + bias - gt[c]);
+        float r = om * (gain * im[c] + bias - gt[c]);
+        if constexpr (DEPTH) r *= PD.w_rgb;            // alpha * rgb_pp, Huber after the weighting
         l1 += fabsf(r);
         const float h = huber(r, P.obj.huber_delta, dh);
         float phi, gam;
         norm_terms(h, P.obj.p1 ? 1.f : 2.f, phi, gam);
         acc += phi;
-        const float gr = gam * dh * om;
+        float gr = gam * dh * om;
+        if constexpr (DEPTH) gr *= PD.w_rgb;
         ga += gr * im[c];
         gb += gr;
         P.obj.grad_image[c * HW + pix] = gr * gain;
+      }
+      if constexpr (DEPTH) {
+        // r_d = (1 - alpha) (depth dm - gt_depth dm), dm = (gt_depth > 0.01) & (opacity > 0.95): the rendered depth
+        // and opacity are the wave's own registers; the row does not touch the exposure sums
+        const float gtd = PD.gt_depth[pix];
+        const float dm = (gtd > PD.depth_thr && 1.f - T > PD.opa_thr) ? 1.f : 0.f;
+        const float rd = PD.w_depth * (C2D.y * dm - gtd * dm);
+        float dh, phi, gam;
+        l1 += fabsf(rd);
+        const float h = huber(rd, P.obj.huber_delta, dh);
+        norm_terms(h, P.obj.p1 ? 1.f : 2.f, phi, gam);
+        acc += phi;
+        PD.grad_depth[pix] = gam * dh * PD.w_depth * dm;
       }
     }
 #pragma unroll
@@ -1122,6 +1138,11 @@ __global__ __launch_bounds__(64, 6) void k_blend_fwd(KP P) {
     }
   }
 }
+
+template <bool OBJ>
+__global__ __launch_bounds__(64, 6) void k_blend_fwd(KP P) { blend_fwd<OBJ, false>(P, KObjDepth{}); }
+
+__global__ __launch_bounds__(64, 6) void k_blend_fwd_rgbd(KP P, KObjDepth PD) { blend_fwd<true, true>(P, PD); }
 
 // ---------------------------------------------------------------------------------
 static inline int check_launch() {
@@ -1178,7 +1199,7 @@ int launch_forward_project(const KP& P, hipStream_t st) {
   return check_launch();
 }
 
-int launch_forward_blend(const KP& P, hipStream_t st) {
+int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD) {
   // cursors restart at 0 on every call so a retry with a larger capacity is valid
   // (n_touched is zeroed by the emit pass of the LDS path)
   if (P.T <= kBinMaxTilesLds) {
@@ -1211,7 +1232,9 @@ int launch_forward_blend(const KP& P, hipStream_t st) {
 #else
   constexpr int kFwdGridChunk = kFwdChunk;
 #endif
-  if (P.obj.on) launch("blend_fwd", k_blend_fwd<true>, dim3(grid_pad(4 * P.T, kFwdGridChunk)), dim3(64), st, P);
+  if (P.obj.on && PD && PD->gt_depth)
+    launch("blend_fwd_rgbd", k_blend_fwd_rgbd, dim3(grid_pad(4 * P.T, kFwdGridChunk)), dim3(64), st, P, *PD);
+  else if (P.obj.on) launch("blend_fwd", k_blend_fwd<true>, dim3(grid_pad(4 * P.T, kFwdGridChunk)), dim3(64), st, P);
   else launch("blend_fwd", k_blend_fwd<false>, dim3(grid_pad(4 * P.T, kFwdGridChunk)), dim3(64), st, P);
   return check_launch();
 }

@@ -46,6 +46,14 @@ struct KObj {
   float* partial;                                     // [4][4T]: sum |h|^p | d/da | d/db | sum |r|, one entry per quadrant wave
 };
 
+// RGB-D form of the objective (k_blend_fwd_rgbd, mgs_tracking_iteration_rgbd): the depth row stacked under the colour
+// rows.  A second kernel argument of that kernel alone - KP keeps its size, so no other kernel's argument layout moves.
+struct KObjDepth {
+  const float* gt_depth;                              // [H*W]
+  float* grad_depth;                                  // [H*W]
+  float w_rgb, w_depth, depth_thr, opa_thr;           // alpha, 1 - alpha, 0.01, 0.95
+};
+
 struct KP {
   int N, W, H, grid_x, grid_y, T, deg, K, cap;
   int pack;                // 1: sort key low word = id << kPackBits | pair index (no payload array)

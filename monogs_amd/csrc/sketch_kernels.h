@@ -42,8 +42,12 @@ struct SketchKeys { int on, chunk, bits; unsigned int k0, k1, k2; };   // on != 
 
 // One workgroup's share of the sketched residual pass (block `bid` of `nblocks`, kSketchThreads threads); s_acc =
 // 3 * stack * sketch floats of LDS ([d][3]: Sf, d/da, d/db), s_red = kSketchThreads / 64 floats.
+// DEPTH (RGB-D tracking, include/monogs_raster.h: mgs_tracking_depth_args): the colour rows take the factor w_rgb and
+// the depth row r_d joins the pixel's bucket sum - loss_tracking_img.sum(dim=0) of slam_frontend.py:640 over four rows.
+template <bool DEPTH = false>
 __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_args& A, const SketchKeys& K, float* s_acc,
-                                                      float* s_red, int bid, int nblocks) {
+                                                      float* s_red, int bid, int nblocks,
+                                                      const mgs_tracking_depth_args* D = nullptr) {
   const int d = A.stack_dim * A.sketch_dim;
   for (int i = threadIdx.x; i < 3 * d; i += kSketchThreads) s_acc[i] = 0.f;
   __syncthreads();
@@ -78,14 +82,25 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const float im = A.image[c * HW + p];
-      const float r = om * (gain * im + bias - A.gt[c * HW + p]);
+      float r = om * (gain * im + bias - A.gt[c * HW + p]);
+      if constexpr (DEPTH) r *= D->w_rgb;
       l1 += fabsf(r);
       float dh;
       hs += huber(r, A.huber_delta, dh);
-      const float g = w * dh * om;              // d weighted / d (gain * image + bias)
+      float g = w * dh * om;                    // d weighted / d (gain * image + bias)
+      if constexpr (DEPTH) g *= D->w_rgb;
       A.grad_image[c * HW + p] = g * gain_bwd;
       da += g * im;
       db += g;
+    }
+    if constexpr (DEPTH) {
+      const float gtd = D->gt_depth[p];
+      const float dm = (gtd > D->depth_threshold && A.opacity[p] > D->opacity_threshold) ? 1.f : 0.f;
+      const float rd = D->w_depth * (D->depth[p] * dm - gtd * dm);
+      l1 += fabsf(rd);
+      float dh;
+      hs += huber(rd, A.huber_delta, dh);
+      D->grad_depth[p] = w * dh * D->w_depth * dm;
     }
     if (b >= 0 && b < d) {
       atomicAdd(&s_acc[3 * b], w * hs);
@@ -119,6 +134,7 @@ struct SketchFuse {
   const mgs_sketch_residual_args* residual;
   SketchKeys keys;
   int skip_prep;
+  const mgs_tracking_depth_args* depth;     // RGB-D residual pass (depth row), or null
 };
 
 inline bool sketch_keys(int64_t num_pixels, int32_t stack_dim, int32_t sketch_dim, uint64_t key, SketchKeys& K) {

@@ -419,6 +419,76 @@ __global__ __launch_bounds__(kLossBlock) void k_track_loss_onepass(mgs_tracking_
   }
 }
 
+// RGB-D form of k_track_loss_onepass (mgs_tracking_loss_rgbd_fused): the three colour rows weighted by w_rgb and the
+// depth row r_d = w_depth (depth dm - gt_depth dm) per pixel, in that order (the arithmetic of k_blend_fwd<true, true>'s
+// epilogue).  Same partial layout; d/d depth (un-normalised) into D.grad_depth.
+__global__ __launch_bounds__(kLossBlock) void k_track_loss_rgbd(mgs_tracking_loss_args A, mgs_tracking_depth_args D) {
+  __shared__ float s_red[kLossBlock / 64];
+  const float a = A.exposure_a[0];
+  const float gain = fabsf(a) + A.exposure_eps, bias = A.exposure_b[0];
+  const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
+  const size_t HW = (size_t)A.num_pixels;
+  const float pn = norm_p(A.pnorm);
+  float acc = 0.f, ga = 0.f, gb = 0.f, l1 = 0.f;
+  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
+    const float opa = A.opacity[p];
+    const float om = opa * (A.mask ? A.mask[p] : 1.f);
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float im = A.image[c * HW + p];
+      float dh, phi, gam;
+      const float r = om * (gain * im + bias - A.gt[c * HW + p]) * D.w_rgb;
+      l1 += fabsf(r);
+      const float h = huber(r, A.huber_delta, dh);
+      norm_terms(h, pn, phi, gam);
+      acc += phi;
+      const float gr = gam * dh * om * D.w_rgb;
+      ga += gr * im;
+      gb += gr;
+      A.grad_image[c * HW + p] = gr * gain;
+    }
+    const float gtd = D.gt_depth[p];
+    const float dm = (gtd > D.depth_threshold && opa > D.opacity_threshold) ? 1.f : 0.f;
+    const float rd = D.w_depth * (D.depth[p] * dm - gtd * dm);
+    float dh, phi, gam;
+    l1 += fabsf(rd);
+    const float h = huber(rd, A.huber_delta, dh);
+    norm_terms(h, pn, phi, gam);
+    acc += phi;
+    D.grad_depth[p] = gam * dh * D.w_depth * dm;
+  }
+  const float t = block_sum(acc, s_red);
+  const float ta = block_sum(ga, s_red);
+  const float tb = block_sum(gb, s_red);
+  const float tl = block_sum(l1, s_red);
+  if (threadIdx.x == 0) {
+    A.partial[blockIdx.x] = t;
+    A.partial[gridDim.x + blockIdx.x] = ta * sgn;
+    A.partial[2 * gridDim.x + blockIdx.x] = tb;
+    A.partial[3 * gridDim.x + blockIdx.x] = tl;
+  }
+}
+
+// scalars[0] = loss, scalars[1] = loss^(1-p); grad_a / grad_b = the exposure sums times loss^(1-p) (when not NULL)
+__global__ __launch_bounds__(kLossBlock) void k_track_loss_rgbd_finish(mgs_tracking_loss_args A, int nblk) {
+  __shared__ float s_red[kLossBlock / 64];
+  float s = 0.f, x = 0.f, y = 0.f;
+  for (int i = threadIdx.x; i < nblk; i += kLossBlock) {
+    s += A.partial[i]; x += A.partial[nblk + i]; y += A.partial[2 * nblk + i];
+  }
+  const float ts = block_sum(s, s_red);
+  const float tx = block_sum(x, s_red);
+  const float ty = block_sum(y, s_red);
+  if (threadIdx.x == 0) {
+    float l, sc;
+    norm_finish(ts, norm_p(A.pnorm), l, sc);
+    A.scalars[0] = l;
+    A.scalars[1] = sc;
+    if (A.grad_a) A.grad_a[0] = tx * sc;
+    if (A.grad_b) A.grad_b[0] = ty * sc;
+  }
+}
+
 // ---------------------------------------------------------------------------------
 // Damped least squares of the sketched LM step (utils/slam_frontend.py:672-697):
 //   x = argmin || [SJ; sqrt(lambda) I] x + [Sf; 0] ||   <=>   (SJ^T SJ + lambda I) x = -SJ^T Sf
@@ -819,6 +889,13 @@ __global__ __launch_bounds__(kSketchThreads) void k_sketch_residual(mgs_sketch_r
   sketch_residual_block(A, K, s_acc, s_red, blockIdx.x, gridDim.x);
 }
 
+__global__ __launch_bounds__(kSketchThreads) void k_sketch_residual_rgbd(mgs_sketch_residual_args A, SketchKeys K,
+                                                                        mgs_tracking_depth_args D) {
+  extern __shared__ float s_acc[];   // [d][3]: Sf, d/da, d/db
+  __shared__ float s_red[kSketchThreads / 64];
+  sketch_residual_block<true>(A, K, s_acc, s_red, blockIdx.x, gridDim.x, &D);
+}
+
 static int loss_blocks(int64_t hw) {
   const int64_t b = (hw + kLossBlock - 1) / kLossBlock;
   return (int)(b < kLossBlocks ? (b < 1 ? 1 : b) : kLossBlocks);
@@ -928,6 +1005,22 @@ int32_t mgs_sketch_residual(const mgs_sketch_residual_args* a, void* stream) {
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
+int32_t mgs_sketch_residual_rgbd(const mgs_sketch_residual_args* a, const mgs_tracking_depth_args* d, void* stream) {
+  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->bucket ||
+      !a->weights || !a->grad_image || !a->Sf || !a->sj_exposure || !a->l1 || a->num_pixels < 1 ||
+      a->stack_dim < 1 || a->sketch_dim < 1 || !d || !d->depth || !d->gt_depth || !d->grad_depth)
+    return MGS_ERR_BAD_ARGUMENT;
+  const size_t smem = sizeof(float) * 3 * (size_t)a->stack_dim * a->sketch_dim;
+  if (smem > 48 * 1024) return MGS_ERR_UNSUPPORTED;
+  const int64_t want = (a->num_pixels + kSketchThreads - 1) / kSketchThreads;
+  const int nb = (int)(want < kSketchBlocks ? want : kSketchBlocks);
+  SketchKeys K = {0, 0, 0, 0u, 0u, 0u};
+  if (a->assign && !sketch_keys(a->num_pixels, a->stack_dim, a->sketch_dim, a->assign_key, K)) return MGS_ERR_BAD_ARGUMENT;
+  launch_smem("sketch_residual_rgbd", k_sketch_residual_rgbd, dim3(nb), dim3(kSketchThreads), smem, (hipStream_t)stream,
+              *a, K, *d);
+  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
 int32_t mgs_tracking_loss_partial_count(int64_t num_pixels) { return 4 * loss_blocks(num_pixels); }
 
 // p of the norm: <= 0 selects 2; 0 < p < 1 is not a norm (and its derivative is unbounded at 0)
@@ -962,6 +1055,20 @@ int32_t mgs_tracking_loss_onepass(const mgs_tracking_loss_args* a, int32_t* nblk
   } else {
     launch("track_loss", k_track_loss_onepass<false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   }
+  if (nblk_out) *nblk_out = nb;
+  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
+int32_t mgs_tracking_loss_rgbd_fused(const mgs_tracking_loss_args* a, const mgs_tracking_depth_args* d,
+                                     int32_t* nblk_out, void* stream) {
+  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
+      !a->grad_image || a->num_pixels < 1 || !d || !d->depth || !d->gt_depth || !d->grad_depth)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
+  const int nb = loss_blocks(a->num_pixels);
+  launch("track_loss_rgbd", k_track_loss_rgbd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a, *d);
+  if (a->scalars)
+    launch("track_loss_rgbd_fin", k_track_loss_rgbd_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
   if (nblk_out) *nblk_out = nb;
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }

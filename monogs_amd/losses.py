@@ -1,9 +1,9 @@
 """Loss glue of the tracking / mapping inner loops (host side, PyTorch elementwise ops).
 
 Mirrors /root/reference utils/slam_utils.py: HuberLoss (:58-75), ApplyExposure with the
-sketched exposure Jacobian (:115-185), get_loss_tracking_per_pixel (:188-205) and
-get_loss_mapping (:224-253).  These define which rasteriser outputs receive gradient; they
-are not part of the native hot path.  `viewpoint` only needs the attributes used below.
+sketched exposure Jacobian (:115-185), get_loss_tracking_per_pixel (:188-205), its RGB-D form
+completed as a stacked residual (get_loss_tracking_stacked, :208-221) and get_loss_mapping (:224-253).
+These define which rasteriser outputs receive gradient; they are not part of the native hot path.  `viewpoint` only needs the attributes used below.
 """
 from __future__ import annotations
 
@@ -81,6 +81,27 @@ def get_loss_tracking_per_pixel(config, image, depth, opacity, viewpoint, forwar
     gt = viewpoint.original_image.to(image.device)
     m = viewpoint.rgb_pixel_mask_mapping
     return opacity * (image_ab * m - gt * m)
+
+
+def get_loss_tracking_stacked(config, image, depth, opacity, viewpoint, forward_sketch_args=None):
+    """Per-pixel tracking residual with the depth row STACKED under the colour rows, [4,H,W] for RGB-D:
+    the reference's unfinished get_loss_tracking_rgbd_per_pixel (slam_utils.py:208-221) with its two terms
+    concatenated along the channel axis instead of added, so that the tracking loop (best-iterate L1, Huber + norm,
+    the second order's sum over channels) runs unchanged on it:
+        r = cat([alpha * rgb_pp, (1 - alpha) * depth_pp]),  depth_pp = depth * dm - gt_depth * dm,
+        dm = (gt_depth > 0.01) & (opacity > 0.95)
+    rgb_pp is get_loss_tracking_per_pixel's monocular residual (same exposure, sketch mode included); the depth row
+    does not depend on the exposure.  For a monocular config this IS get_loss_tracking_per_pixel."""
+    mono = config["Training"]["monocular"]
+    if mono:
+        return get_loss_tracking_per_pixel(config, image, depth, opacity, viewpoint, forward_sketch_args)
+    rgb_pp = get_loss_tracking_per_pixel({"Training": {"monocular": True}}, image, depth, opacity, viewpoint,
+                                         forward_sketch_args)
+    alpha = config["Training"].get("alpha", 0.95)
+    gt_depth = viewpoint.gt_depth.to(device=depth.device, dtype=torch.float32).view(*depth.shape)
+    dm = (gt_depth > 0.01) & (opacity > 0.95).view(*depth.shape)
+    depth_pp = depth * dm - gt_depth * dm
+    return torch.cat([alpha * rgb_pp, (1 - alpha) * depth_pp], dim=0)
 
 
 def get_loss_mapping(config, image, depth, viewpoint, opacity=None, initialization=False):

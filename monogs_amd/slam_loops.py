@@ -111,12 +111,14 @@ def make_pose_optimizer(viewpoint: ViewCamera, config=DEFAULT_CONFIG):
 
 
 def tracking_step_first_order(viewpoint, gaussians, pose_optimizer, background, pipe=Pipe,
-                              config=DEFAULT_CONFIG):
+                              config=DEFAULT_CONFIG, residual_fn=None):
     """One first-order tracking iteration (slam_frontend.py:493-630): render, per-pixel
-    residual, Huber + L2 norm (or the RGN.pnorm-norm without Huber, :596-600), backward, Adam on (rot, trans, exposure), update_pose."""
+    residual, Huber + L2 norm (or the RGN.pnorm-norm without Huber, :596-600), backward, Adam on (rot, trans, exposure), update_pose.
+    `residual_fn` (default get_loss_tracking_per_pixel) forms the per-pixel residual; losses.get_loss_tracking_stacked
+    gives the RGB-D objective."""
+    residual_fn = get_loss_tracking_per_pixel if residual_fn is None else residual_fn
     render_pkg = render(viewpoint, gaussians, pipe, background)
-    res = get_loss_tracking_per_pixel(config, render_pkg["render"], render_pkg["depth"],
-                                      render_pkg["opacity"], viewpoint)
+    res = residual_fn(config, render_pkg["render"], render_pkg["depth"], render_pkg["opacity"], viewpoint)
     # the reference's best-iterate criterion: ||residual||_1 before Huber (slam_frontend.py:510)
     render_pkg["tracking_l1"] = res.detach().abs().sum()
     delta, p = tracking_norm(config)
@@ -210,21 +212,23 @@ def sketch_args_from_buckets(bucket: torch.Tensor, weights: torch.Tensor, height
 
 def tracking_step_second_order(viewpoint, gaussians, background, lambda_, repeat_dim=1,
                                stack_dim=16, sketch_dim=64, pipe=Pipe, config=DEFAULT_CONFIG,
-                               generator=None, fused_solve=False, fsa=None, return_pkg=False):
+                               generator=None, fused_solve=False, fsa=None, return_pkg=False, residual_fn=None):
     """One sketched Levenberg-Marquardt iteration (slam_frontend.py:484-710): sketched
     render, bucket-summed residual Sf, `repeat_dim` backward passes harvesting the sketched
     Jacobian SJ[(repeat*stack*sketch), 8], damped least squares, left-multiplicative pose
     step and exposure step.  `lambda_` is the damping, or a callable that maps this render's L1
     residual (the reference's loss_tracking_scalar) to it - the trust-region rule of :536-545 needs
-    the current loss before the solve.  Returns (l1, x, SJ, Sf[, render_pkg])."""
+    the current loss before the solve.  `residual_fn` as for tracking_step_first_order (the sum over the residual's
+    rows, :640, takes a depth row like a colour row).  Returns (l1, x, SJ, Sf[, render_pkg])."""
+    residual_fn = get_loss_tracking_per_pixel if residual_fn is None else residual_fn
     H, W = viewpoint.image_height, viewpoint.image_width
     m, dper = H * W, stack_dim * sketch_dim
     if fsa is None:
         fsa = gen_forward_sketch_args(H, W, repeat_dim, stack_dim, sketch_dim, viewpoint.device,
                                       generator)
     render_pkg = render(viewpoint, gaussians, pipe, background, forward_sketch_args=fsa)
-    res = get_loss_tracking_per_pixel(config, render_pkg["render"], render_pkg["depth"],
-                                      render_pkg["opacity"], viewpoint, forward_sketch_args=fsa)
+    res = residual_fn(config, render_pkg["render"], render_pkg["depth"], render_pkg["opacity"], viewpoint,
+                      forward_sketch_args=fsa)
     l1 = res.detach().abs().sum()      # loss_tracking_scalar (slam_frontend.py:510): before Huber
     if callable(lambda_):
         lambda_ = lambda_(l1)
@@ -286,7 +290,7 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
                 use_first_order_best=True, use_best_loss=True, pipe=Pipe, config=DEFAULT_CONFIG,
                 stack_dim=16, sketch_dim=64, initial_lambda=1e-3, min_lambda=1e-6, max_lambda=1e7,
                 increase_factor=5.0, decrease_factor=5.0, second_order_converged_threshold=1e-5,
-                generator=None, fused=False, fsa_fn=None, repeat_dim=1, trace=None):
+                generator=None, fused=False, fsa_fn=None, repeat_dim=1, trace=None, residual_fn=None):
     """The reference's tracking loop for one frame, reference-shaped Python on the HIP rasteriser
     (slam_frontend.py:455-822 with override_mode "none"): first-order iterations (Adam on the pose
     deltas and the exposure; a converged one leaves the whole loop, :623-626), then sketched LM
@@ -296,7 +300,10 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
     at the best state and returns ITS render_pkg (`use_best_loss`, :819-822).
     Returns (render_pkg, best_l1, best_iteration, iterations).  `fsa_fn(i)` may supply the sketch
     arguments of second-order iteration i (tests: the native tracker's partitions).  `trace` (a list)
-    receives per iteration (L1 of its render, |step| it took, converged)."""
+    receives per iteration (L1 of its render, |step| it took, converged).  `residual_fn`: the per-pixel residual of
+    both orders (default get_loss_tracking_per_pixel; losses.get_loss_tracking_stacked for RGB-D, non-fused only)."""
+    if fused and residual_fn is not None:
+        raise ValueError("residual_fn needs the autograd first-order step (fused=False)")
     if fused:
         from .tracking_fused import FusedPoseOptimizer
         lr = config["Training"]["lr"]
@@ -324,7 +331,10 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
             best_state.assign(viewpoint)
         state = TempCamera(viewpoint)            # the state this iteration renders
         if not second:
-            _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config)
+            if residual_fn is None:
+                _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config)
+            else:
+                _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config, residual_fn=residual_fn)
             converged = bool(converged)
             l1 = float(pkg["tracking_l1"])
             step_norm = pkg.get("tracking_step_norm")
@@ -332,7 +342,7 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
             fsa = None if fsa_fn is None else fsa_fn(itr - first_order_iters)
             l1_t, x, _, _, pkg = tracking_step_second_order(
                 viewpoint, gaussians, background, lambda_rule, repeat_dim, stack_dim, sketch_dim, pipe, config,
-                generator, fused_solve=True, fsa=fsa, return_pkg=True)
+                generator, fused_solve=True, fsa=fsa, return_pkg=True, residual_fn=residual_fn)
             l1 = float(l1_t)
             step_norm = x.norm()
             converged = bool(step_norm < second_order_converged_threshold)

@@ -137,10 +137,14 @@ def keyframe_depth(frame_image, depth, opacity, sensor_depth=None, generator=Non
 def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: int = 5, window_size: int = 8,
                  init_iters: int = 1050, mapping_iters: int = 150, first_order_iters: int = 40,
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
-                 use_first_order_best: bool = True, use_best_loss: bool = True):
+                 use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
+                 alpha: float = 0.95):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
-    of the monocular prior / rendered depth."""
+    of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
+    the stacked RGB-D objective against its depth (NativeTracker(gt_depth=..., alpha=alpha))."""
+    if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
+        raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
     H, W = cam.H, cam.W
     fovx, fovy = 2 * math.atan(cam.tanfovx), 2 * math.atan(cam.tanfovy)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -184,7 +188,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         vp = camera(fr, cams[k - 1].T.detach().clone())           # previous pose (:358-362)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        trk = NativeTracker(vp, gm, bg)
+        trk = NativeTracker(vp, gm, bg, gt_depth=fr.depth if rgbd_tracking else None, alpha=alpha)
         if second_order_iters > 0:
             trk.enable_second_order(stack_dim=16, sketch_dim=64, initial_lambda=1e-3, seed=seed + k)
         # one frame of the reference's loop incl. its best-iterate bookkeeping (slam_frontend.py:455-822;

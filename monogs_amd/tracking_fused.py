@@ -80,6 +80,66 @@ def tracking_loss(image, opacity, viewpoint, huber_delta=0.01, pnorm=2.0):
                                viewpoint.exposure_b, viewpoint.exposure_eps, huber_delta, pnorm)
 
 
+class _TrackingLossRGBD(torch.autograd.Function):
+    """Value and the un-normalised gradients in the forward (mgs_tracking_loss_rgbd_fused: two launches); the
+    backward scales them by grad_out * loss^(1-p) on the device - no launch of ours and no host sync."""
+
+    @staticmethod
+    def forward(ctx, image, depth, opacity, gt, mask, gt_depth, exposure_a, exposure_b, exposure_eps, alpha,
+                huber_delta, pnorm):
+        dev = image.device
+        if dev.type != "cuda":
+            raise RuntimeError("fused RGB-D tracking loss runs on the GPU only; use monogs_amd.losses on CPU")
+        lib = _cabi.lib()
+        f = lambda t: None if t is None else t.detach().float().contiguous()
+        image_c, depth_c, opa_c, gt_c, mask_c, gtd_c = f(image), f(depth), f(opacity), f(gt), f(mask), f(gt_depth)
+        HW = int(image_c.shape[-1] * image_c.shape[-2])
+        if depth_c.numel() != HW or gtd_c.numel() != HW or opa_c.numel() != HW:
+            raise ValueError("depth, gt_depth and opacity must hold one value per pixel")
+        partial = torch.empty(int(lib.mgs_tracking_loss_partial_count(HW)), dtype=torch.float32, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)         # loss, loss^(1-p), d/da, d/db
+        g_img = torch.empty_like(image_c)
+        g_dep = torch.empty_like(depth_c)
+        a = _cabi.TrackingLossArgs()
+        a.image, a.opacity, a.gt = image_c.data_ptr(), opa_c.data_ptr(), gt_c.data_ptr()
+        a.mask = None if mask_c is None else mask_c.data_ptr()
+        a.exposure_a, a.exposure_b = exposure_a.data_ptr(), exposure_b.data_ptr()
+        a.exposure_eps, a.huber_delta, a.num_pixels = float(exposure_eps), float(huber_delta), HW
+        a.pnorm = float(pnorm)
+        a.partial, a.scalars = partial.data_ptr(), out.data_ptr()
+        a.grad_image, a.grad_a, a.grad_b = g_img.data_ptr(), out[2:].data_ptr(), out[3:].data_ptr()
+        d = _cabi.TrackingDepthArgs()
+        d.depth, d.gt_depth, d.grad_depth = depth_c.data_ptr(), gtd_c.data_ptr(), g_dep.data_ptr()
+        d.w_rgb, d.w_depth = float(alpha), 1.0 - float(alpha)
+        d.depth_threshold, d.opacity_threshold = 0.01, 0.95
+        _cabi.check(lib.mgs_tracking_loss_rgbd_fused(C.byref(a), C.byref(d), None, _stream(dev)),
+                    "mgs_tracking_loss_rgbd_fused")
+        ctx.save_for_backward(g_img, g_dep, out)
+        ctx.shapes = (image.shape, depth.shape, exposure_a.shape, exposure_b.shape)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        if grad_out is None:
+            return (None,) * 12
+        g_img, g_dep, out = ctx.saved_tensors
+        si, sd, sa, sb = ctx.shapes
+        go = grad_out.detach().float()
+        k = go * out[1]
+        return ((g_img * k).view(si), (g_dep * k).view(sd), None, None, None, None,
+                (out[2] * go).reshape(sa), (out[3] * go).reshape(sb), None, None, None, None)
+
+
+def tracking_loss_rgbd(image, depth, opacity, viewpoint, alpha=0.95, huber_delta=0.01, pnorm=2.0):
+    """|| Huber( r ) ||_p of the stacked RGB-D residual r = losses.get_loss_tracking_stacked (colour rows times alpha,
+    the masked depth row times 1 - alpha) for `viewpoint` (original_image, rgb_pixel_mask_mapping, gt_depth,
+    exposure_a/b/eps); differentiable w.r.t. image, depth and the exposure.  One pass of the HIP kernel
+    (mgs_tracking_loss_rgbd_fused) forms value and gradients; any p >= 1."""
+    return _TrackingLossRGBD.apply(image, depth, opacity, viewpoint.original_image, viewpoint.rgb_pixel_mask_mapping,
+                                   viewpoint.gt_depth, viewpoint.exposure_a, viewpoint.exposure_b,
+                                   viewpoint.exposure_eps, alpha, huber_delta, pnorm)
+
+
 class FusedPoseOptimizer:
     """Adam on (cam_rot_delta, cam_trans_delta, exposure_a, exposure_b) + update_pose in ONE
     launch.  `step()` returns a device int32 flag tensor (1 = converged): reading it is the

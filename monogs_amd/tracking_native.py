@@ -32,11 +32,14 @@ class NativeTracker:
 
     def __init__(self, viewpoint, gaussians, background, huber_delta=0.01, lr_rot=0.003,
                  lr_trans=0.001, lr_a=0.02, lr_b=0.02, betas=(0.9, 0.999), eps=1e-8,
-                 converged_threshold=1e-4, capacity_margin=1.5, pnorm=2.0):
+                 converged_threshold=1e-4, capacity_margin=1.5, pnorm=2.0, gt_depth=None, alpha=0.95):
         # (huber_delta, pnorm) as slam_loops.tracking_norm(config) returns them: the reference's first-order
         # objective is Huber + L2 when RGN.use_huber, else the RGN.pnorm-norm without Huber (huber_delta = 0),
         # slam_frontend.py:596-600.  p = 1 and p = 2 ride in the forward blend's epilogue, any other p >= 1
         # costs one more launch per iteration.
+        # gt_depth ([H,W] or [1,H,W] sensor depth): RGB-D tracking - the objective is the stacked residual of
+        # losses.get_loss_tracking_stacked (colour rows times `alpha`, the masked depth row times 1 - alpha) in every
+        # first- and second-order iteration (the *_rgbd entry points); None keeps the monocular launch sequence.
         vp = viewpoint
         dev = vp.T.device
         if dev.type != "cuda":
@@ -98,6 +101,17 @@ class NativeTracker:
         self.capacity_margin = capacity_margin
         self._alloc_bins(a, max(1024, int(D * capacity_margin)))
 
+        self.depth_args = None
+        if gt_depth is not None:
+            if gt_depth.numel() != H * W:
+                raise ValueError(f"gt_depth must hold H*W = {H * W} values, got {tuple(gt_depth.shape)}")
+            self.gt_depth = f32(gt_depth).reshape(1, H, W)
+            self.grad_depth = torch.empty(1, H, W, device=dev)
+            d = _cabi.TrackingDepthArgs()
+            d.depth, d.gt_depth, d.grad_depth = self.depth.data_ptr(), self.gt_depth.data_ptr(), self.grad_depth.data_ptr()
+            d.w_rgb, d.w_depth = float(alpha), 1.0 - float(alpha)
+            d.depth_threshold, d.opacity_threshold = 0.01, 0.95
+            self.depth_args = d
         self.grad_image = torch.empty(3, H, W, device=dev)
         self.grad_tau = torch.zeros(6, device=dev)
         self.grad_exposure = torch.zeros(2, device=dev)
@@ -205,8 +219,13 @@ class NativeTracker:
         so.base.camera_matrices_valid = 1 if self._matrices_fresh else 0
         self.so_t += 1
         so.key = (self.so_seed * 0x9E3779B97F4A7C15 + self.so_t) & 0xFFFFFFFFFFFFFFFF
-        _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order(C.byref(so), self._stream()),
-                    "mgs_tracking_iteration_second_order")
+        if self.depth_args is None:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order(C.byref(so), self._stream()),
+                        "mgs_tracking_iteration_second_order")
+        else:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order_rgbd(C.byref(so), C.byref(self.depth_args),
+                                                                             self._stream()),
+                        "mgs_tracking_iteration_second_order_rgbd")
         self._matrices_fresh = True      # the LM kernel wrote the matrices of the stepped pose
         return self.lm_state
 
@@ -243,8 +262,13 @@ class NativeTracker:
         # pinned, written by every forward: no sync needed to read the previous iteration's value
         self.args.fwd.big_tile_pass = -1 if 0 < int(self._host_D[1]) <= 900 else 0
         self.args.camera_matrices_valid = 1 if self._matrices_fresh else 0
-        _cabi.check(_cabi.lib().mgs_tracking_iteration(C.byref(self.args), self._stream()),
-                    "mgs_tracking_iteration")
+        if self.depth_args is None:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration(C.byref(self.args), self._stream()),
+                        "mgs_tracking_iteration")
+        else:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration_rgbd(C.byref(self.args), C.byref(self.depth_args),
+                                                                self._stream()),
+                        "mgs_tracking_iteration_rgbd")
         self._matrices_fresh = True      # the Adam kernel wrote the matrices of the updated pose
         return self.converged
 
@@ -293,7 +317,7 @@ class NativeTracker:
 
     @property
     def best_loss(self):
-        """||residual||_1 of the best iterate so far (device scalar; inf before the first iteration)."""
+        """||residual||_1 (all rows: four per pixel in RGB-D mode) of the best iterate so far (device scalar; inf before the first iteration)."""
         return self.best[0]
 
     @property
