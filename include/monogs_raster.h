@@ -204,7 +204,7 @@ int32_t mgs_abi_version(void);
  * 11 = mgs_adam_group, 12 = mgs_map_plan_args, 13 = mgs_gather_tensor, 14 = mgs_map_gather_args,
  * 15 = mgs_map_accum_args, 16 = mgs_map_activate_args, 17 = mgs_mapping_view_args,
  * 18 = mgs_map_finish_args, 19 = mgs_map_append_args, 20 = mgs_ssim_loss_args,
- * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args);
+ * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args, 23 = mgs_tracking_sample_args);
  * -1 for an unknown index.  Lets a foreign-language binding verify its struct mirrors. */
 int32_t mgs_struct_size(int32_t which);
 const char* mgs_status_string(int32_t status);
@@ -612,6 +612,36 @@ int32_t mgs_tracking_loss_rgbd_fused(const mgs_tracking_loss_args* args, const m
 /* mgs_sketch_residual with the depth row: hs += Huber(r_d) into the pixel's bucket, l1 += |r_d|,
  * grad_depth = weight * Huber'(r_d) * w_depth * dm. */
 int32_t mgs_sketch_residual_rgbd(const mgs_sketch_residual_args* args, const mgs_tracking_depth_args* depth, void* stream);
+
+/* ---- pixel-sampled first-order tracking ("Pixel-sampled first-order tracking") ---------------
+ * The reference's RGN.first_order.num_pixels > 0 branch (utils/slam_frontend.py:573-592), with the scaling defined for
+ * every norm.  The forward and the objective's value are full-image; only the gradient is estimated:
+ *   v_i = sum_c |r_ic| + 1e-8,  q_i = v_i / sum_j v_j,  i_1..i_K iid ~ q,
+ *   g = (1/p) Phi^(1-p) (1/K) sum_k grad psi_{i_k} / q_{i_k},  psi_i = sum_c |h(r_ic)|^p,  Phi = (sum_i psi_i)^(1/p)
+ * (unbiased for grad Phi: pose and exposure rows alike).  The draw is keyed by `key` (counter-based hash, no host sync)
+ * and its flat pixel indices are written to `indices` IN TILE ORDER (16x16 tiles row-major, then 8x8 quadrants,
+ * then row-major inside a quadrant): the K draws are generated as sorted uniforms, which is the same distribution
+ * as K iid draws.  replay_indices (tests): skip the draw and use these pixels (any order; they are ranked into tile
+ * order, an index outside [0, H*W) gets weight 0; O(K^2) work in one workgroup - not for production use). */
+#define MGS_TRACK_SAMPLE_MAX 65536
+typedef struct mgs_tracking_sample_args {
+  int32_t num_samples;             /* K, 1 .. MGS_TRACK_SAMPLE_MAX (else MGS_ERR_UNSUPPORTED) */
+  int32_t reserved0;
+  uint64_t key;                    /* changes every iteration */
+  int32_t* indices;                /* [K] out: drawn flat pixel indices, tile order */
+  void* scratch;                   /* mgs_tracking_sample_scratch_bytes(shape, K) bytes, no initial state */
+  const int32_t* replay_indices;   /* [K] or NULL */
+  float* grad_out;                 /* [8] or NULL: the estimate before the Phi^(1-p) factor - d tau ([rho; theta], the
+                                      order of mgs_backward_args.grad_tau), d/da, d/db (tests) */
+} mgs_tracking_sample_args;
+
+uint64_t mgs_tracking_sample_scratch_bytes(const mgs_raster_shape* shape, int32_t num_samples);
+/* One first-order iteration with the sampled gradient: camera matrices -> forward (plain blend) -> sampling weights
+ * and exact objective sums -> draw -> sparse pose backward over the K pixels (no per-Gaussian or per-pixel pass) ->
+ * mgs_pose_adam_step with the Phi^(1-p) normalisation and the best-iterate L1, as mgs_tracking_iteration.
+ * depth == NULL: monocular; else the stacked RGB-D residual of mgs_tracking_iteration_rgbd.  Any p >= 1. */
+int32_t mgs_tracking_iteration_sampled(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* depth,
+                                       const mgs_tracking_sample_args* sample, void* stream);
 
 /* ---- map maintenance on the device ---------------------------------- */
 

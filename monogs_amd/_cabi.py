@@ -28,7 +28,7 @@ EXPORTS = (
     "mgs_mapping_loss_fused", "mgs_mapping_view_iteration", "mgs_map_finish_iteration", "mgs_map_append",
     "mgs_ssim_loss_partial_count", "mgs_ssim_loss", "mgs_refine_view_iteration",
     "mgs_tracking_iteration_rgbd", "mgs_tracking_iteration_second_order_rgbd", "mgs_tracking_loss_rgbd_fused",
-    "mgs_sketch_residual_rgbd",
+    "mgs_sketch_residual_rgbd", "mgs_tracking_sample_scratch_bytes", "mgs_tracking_iteration_sampled",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -210,6 +210,13 @@ class TrackingDepthArgs(C.Structure):
                 + [(n, C.c_float) for n in ("w_rgb", "w_depth", "depth_threshold", "opacity_threshold")])
 
 
+class TrackingSampleArgs(C.Structure):
+    _fields_ = [("num_samples", C.c_int32), ("reserved0", C.c_int32), ("key", C.c_uint64), ("indices", _fp),
+                ("scratch", _fp), ("replay_indices", _fp), ("grad_out", _fp)]
+
+
+TRACK_SAMPLE_MAX = 65536
+
 _lib = None
 
 
@@ -324,6 +331,11 @@ def lib():
     L.mgs_tracking_loss_rgbd_fused.argtypes = [C.POINTER(TrackingLossArgs), _dp, C.POINTER(C.c_int32), C.c_void_p]
     L.mgs_sketch_residual_rgbd.restype = C.c_int32
     L.mgs_sketch_residual_rgbd.argtypes = [C.POINTER(SketchResidualArgs), _dp, C.c_void_p]
+    L.mgs_tracking_sample_scratch_bytes.restype = C.c_uint64
+    L.mgs_tracking_sample_scratch_bytes.argtypes = [C.POINTER(RasterShape), C.c_int32]
+    L.mgs_tracking_iteration_sampled.restype = C.c_int32
+    L.mgs_tracking_iteration_sampled.argtypes = [C.POINTER(TrackingIterArgs), _dp, C.POINTER(TrackingSampleArgs),
+                                                 C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")
@@ -336,7 +348,8 @@ def struct_mirrors():
     return [RasterShape, WorkspaceSizes, ForwardArgs, BackwardArgs, PoseAdamArgs, MappingLossArgs,
             LMStepArgs, TrackingLossArgs, TrackingIterArgs, SketchResidualArgs, TrackingSOArgs,
             AdamGroup, MapPlanArgs, GatherTensor, MapGatherArgs, MapAccumArgs, MapActivateArgs,
-            MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs, TrackingDepthArgs]
+            MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs, TrackingDepthArgs,
+            TrackingSampleArgs]
 
 
 def check(status: int, what: str) -> None:

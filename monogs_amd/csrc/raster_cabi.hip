@@ -136,6 +136,7 @@ int32_t mgs_struct_size(int32_t which) {
     case 20: return (int32_t)sizeof(mgs_ssim_loss_args);
     case 21: return (int32_t)sizeof(mgs_refine_view_args);
     case 22: return (int32_t)sizeof(mgs_tracking_depth_args);
+    case 23: return (int32_t)sizeof(mgs_tracking_sample_args);
     default: return -1;
   }
 }
@@ -353,6 +354,77 @@ int32_t mgs_tracking_iteration_rgbd(const mgs_tracking_iter_args* args, const mg
                                     void* stream) {
   if (!depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
   return tracking_iteration_impl(args, depth, stream);
+}
+
+}  // extern "C"
+
+// Pixel-sampled first-order iteration (sampled_tracking.hip): the plain forward, then the sampled objective and its
+// sparse pose backward leave per-tile partials that the Adam kernel sums like those of mgs_tracking_iteration.
+static int32_t tracking_iteration_sampled_impl(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* D,
+                                               const mgs_tracking_sample_args* S, void* stream) {
+  if (!args || !S || !args->one || !args->adam.T || !args->fwd.viewmatrix || !args->fwd.projmatrix ||
+      !S->indices || !S->scratch)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (S->num_samples < 1 || S->num_samples > MGS_TRACK_SAMPLE_MAX) return MGS_ERR_UNSUPPORTED;
+  if (args->fwd.shape.pair_capacity < 1) return MGS_ERR_BAD_ARGUMENT;
+  const mgs_tracking_loss_args& L = args->loss;
+  if (!L.gt || !L.exposure_a || !L.exposure_b || !L.scalars) return MGS_ERR_BAD_ARGUMENT;
+  if (L.pnorm > 0.f && L.pnorm < 1.f) return MGS_ERR_BAD_ARGUMENT;
+  int32_t rc = MGS_OK;
+  KP P;
+  if ((rc = fill_kp(args->fwd, true, true, P)) != MGS_OK) return rc;
+  if (!args->camera_matrices_valid) {
+    rc = mgs_camera_from_pose(args->adam.T, args->fwd.projmatrix_raw, const_cast<float*>(args->fwd.viewmatrix),
+                              const_cast<float*>(args->fwd.projmatrix), stream);
+    if (rc != MGS_OK) return rc;
+  }
+  if ((rc = mgs_raster_forward_project(&args->fwd, stream)) != MGS_OK) return rc;
+  if ((rc = launch_forward_blend(P, (hipStream_t)stream)) != MGS_OK) return rc;
+  const float pn = L.pnorm > 0.f ? L.pnorm : 2.f;
+  const SampLayout SL = samp_layout(P.T, S->num_samples);
+  char* w = static_cast<char*>(S->scratch);
+  KS K{};
+  K.K = S->num_samples; K.T = P.T; K.HW = P.W * P.H; K.replay = S->replay_indices ? 1 : 0; K.rgbd = D ? 1 : 0;
+  K.key = S->key;
+  K.image = args->fwd.out_color; K.opacity = args->fwd.out_opacity; K.depth = args->fwd.out_depth;
+  K.gt = L.gt; K.mask = L.mask; K.exposure_a = L.exposure_a; K.exposure_b = L.exposure_b;
+  K.exposure_eps = L.exposure_eps; K.huber_delta = L.huber_delta; K.pnorm = pn;
+  if (D) {
+    K.gt_depth = D->gt_depth; K.w_rgb = D->w_rgb; K.w_depth = D->w_depth;
+    K.depth_thr = D->depth_threshold; K.opa_thr = D->opacity_threshold;
+  }
+  K.replay_idx = S->replay_indices; K.indices = S->indices; K.grad_out = S->grad_out;
+  K.v = reinterpret_cast<float*>(w + SL.v); K.part = reinterpret_cast<float*>(w + SL.part);
+  K.prefix = reinterpret_cast<double*>(w + SL.prefix); K.target = reinterpret_cast<double*>(w + SL.target);
+  K.pos = reinterpret_cast<int*>(w + SL.pos); K.weight = reinterpret_cast<float*>(w + SL.weight);
+  K.tau_part = reinterpret_cast<float*>(w + SL.tau_part); K.expo_part = reinterpret_cast<float*>(w + SL.expo_part);
+  if ((rc = launch_sampled_pose(P, K, (hipStream_t)stream)) != MGS_OK) return rc;
+  mgs_pose_adam_args A = args->adam;
+  A.grad_trans = nullptr; A.grad_rot = nullptr; A.grad_a = nullptr; A.grad_b = nullptr;
+  A.tau_partials = K.tau_part; A.num_tau_partials = P.T;
+  A.exposure_partials = K.expo_part; A.num_exposure_partials = P.T;
+  A.loss_partials = K.part; A.num_loss_partials = P.T;
+  A.loss_norm_mode = 1; A.loss_grad_out = args->one; A.loss_pnorm = pn;
+  A.loss_view = L.scalars; A.loss_accum = nullptr;
+  A.best = args->best; A.l1_partials = K.part + P.T; A.num_l1_partials = P.T;
+  A.projection = args->fwd.projmatrix_raw;
+  A.viewmatrix_out = const_cast<float*>(args->fwd.viewmatrix);
+  A.projmatrix_out = const_cast<float*>(args->fwd.projmatrix);
+  return mgs_pose_adam_step(&A, stream);
+}
+
+extern "C" {
+
+uint64_t mgs_tracking_sample_scratch_bytes(const mgs_raster_shape* shape, int32_t num_samples) {
+  if (!shape || !shape_ok(*shape) || num_samples < 1 || num_samples > MGS_TRACK_SAMPLE_MAX) return 0;
+  const int T = ((shape->width + kTile - 1) / kTile) * ((shape->height + kTile - 1) / kTile);
+  return samp_layout(T, num_samples).bytes;
+}
+
+int32_t mgs_tracking_iteration_sampled(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* depth,
+                                       const mgs_tracking_sample_args* sample, void* stream) {
+  if (depth && !depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
+  return tracking_iteration_sampled_impl(args, depth, sample, stream);
 }
 
 }  // extern "C"

@@ -218,6 +218,30 @@ constexpr int kBinMaxTilesLds = 12288;   // T above this falls back to global at
 // and Gaussians per workgroup for N Gaussians.
 void bin_grid(int N, int& nblk, int& per);
 
+// Pixel-sampled first-order tracking (sampled_tracking.hip, mgs_tracking_iteration_sampled): objective, draw and
+// scratch of one iteration.  Positions are tile-order: tile * 256 + quadrant-major index inside the tile.
+struct KS {
+  int K, T, HW, replay, rgbd, reserved;
+  unsigned long long key;
+  const float *image, *opacity, *depth, *gt, *mask, *gt_depth, *exposure_a, *exposure_b;
+  float exposure_eps, huber_delta, pnorm, w_rgb, w_depth, depth_thr, opa_thr, pad;
+  const int* replay_idx;   // [K] flat pixel indices or null
+  int* indices;            // [K] out: flat pixel indices of the draw, in tile order
+  float* v;                // [256 T] sampling weights v = sum |r| + 1e-8 (0 outside the image)
+  float* part;             // [3][T] tile sums: |h|^p | |r| | v
+  double* prefix;          // [T + 1] exclusive fp64 prefix of the tile sums of v; [T] = total
+  double* target;          // [K] sorted draws scaled to the total
+  int* pos;                // [K] tile-order positions of the samples (sorted)
+  float* weight;           // [K] 1 / (K q) = total / (K v)
+  float* tau_part;         // [T][6] per-tile d tau (un-normalised)
+  float* expo_part;        // [2][T] per-tile d/da, d/db (un-normalised)
+  float* grad_out;         // [8] or null
+};
+
+struct SampLayout { uint64_t v, part, prefix, target, pos, weight, tau_part, expo_part, bytes; };
+SampLayout samp_layout(int T, int K);
+int launch_sampled_pose(const KP& P, const KS& S, hipStream_t st);
+
 inline Layout make_layout(const mgs_raster_shape& s) {
   Layout L;
   const uint64_t N = (uint64_t)s.num_gaussians;

@@ -116,3 +116,26 @@ def get_loss_mapping(config, image, depth, viewpoint, opacity=None, initializati
     dm = (viewpoint.gt_depth > 0.01).view(*depth.shape)
     l1_depth = torch.abs(depth * dm - viewpoint.gt_depth * dm)
     return alpha * l1_rgb.mean() + (1 - alpha) * l1_depth.mean()
+
+
+def sampled_tracking_surrogate(res, indices, delta, p):
+    """Surrogate of the pixel-sampled first-order objective (DESIGN.md "Pixel-sampled first-order tracking"; the
+    reference's RGN.first_order.num_pixels branch, utils/slam_frontend.py:573-592, with the scaling defined for every
+    norm).  `res` [C, H, W] is the residual BEFORE Huber (C = 3 monocular, 4 stacked RGB-D), `indices` the K drawn
+    flat pixel indices, `delta` the Huber threshold (<= 0: none), `p` the norm.  Returns (surrogate, Phi):
+        surrogate = Phi.detach()^(1-p) / p * (1/K) sum_k psi_{i_k} / q_{i_k}.detach(),   psi_i = sum_c |h(r_ic)|^p,
+        Phi = (sum_i psi_i)^(1/p),   q_i = v_i / sum_j v_j,   v_i = sum_c |r_ic| + 1e-8.
+    Its gradient is the unbiased estimate of grad Phi that the native sampled iteration takes; Phi is exact.
+    For p = 1 without Huber it is the reference's loss_tracking = (1/K) sum_k vec1[i_k] / dist[i_k]."""
+    r = res.reshape(res.shape[0], -1)
+    with torch.no_grad():
+        v = r.abs().sum(0) + 1e-8
+        q = v / v.sum()
+    h = HuberLoss.apply(r, delta) if delta > 0 else r
+    psi = h.abs().pow(p).sum(0)
+    with torch.no_grad():
+        phi = psi.sum().pow(1.0 / p)
+        scale = torch.where(phi > 0, phi.pow(1.0 - p), torch.zeros_like(phi)) / p if p != 1 else torch.ones_like(phi)
+    idx = indices.reshape(-1).to(device=r.device, dtype=torch.long)
+    sur = scale * (psi[idx] / q[idx]).sum() / idx.numel()
+    return sur, phi

@@ -17,7 +17,7 @@ import torch
 import torch.nn as nn
 
 from .gaussian_renderer import render
-from .losses import HuberLoss, get_loss_mapping, get_loss_tracking_per_pixel
+from .losses import HuberLoss, get_loss_mapping, get_loss_tracking_per_pixel, sampled_tracking_surrogate
 from .pose import SE3_exp, update_pose
 
 
@@ -101,6 +101,14 @@ def tracking_norm(config=DEFAULT_CONFIG):
     return 0.0, float(rgn["pnorm"])
 
 
+def sampled_num_pixels(config=DEFAULT_CONFIG) -> int:
+    """RGN.first_order.num_pixels of a config (the commented tracking blocks of configs/mono/tum/base_config.yaml set
+    300): > 0 turns on the pixel-sampled first-order gradient (utils/slam_frontend.py:573-592); -1 when absent."""
+    fo = (config.get("Training", {}).get("RGN", {}) or {}).get("first_order", {}) or {}
+    n = fo.get("num_pixels", -1)
+    return -1 if n is None else int(n)
+
+
 def make_pose_optimizer(viewpoint: ViewCamera, config=DEFAULT_CONFIG):
     lr = config["Training"]["lr"]
     return torch.optim.Adam([
@@ -111,22 +119,36 @@ def make_pose_optimizer(viewpoint: ViewCamera, config=DEFAULT_CONFIG):
 
 
 def tracking_step_first_order(viewpoint, gaussians, pose_optimizer, background, pipe=Pipe,
-                              config=DEFAULT_CONFIG, residual_fn=None):
+                              config=DEFAULT_CONFIG, residual_fn=None, num_pixels=-1, generator=None,
+                              pixel_indices=None):
     """One first-order tracking iteration (slam_frontend.py:493-630): render, per-pixel
     residual, Huber + L2 norm (or the RGN.pnorm-norm without Huber, :596-600), backward, Adam on (rot, trans, exposure), update_pose.
     `residual_fn` (default get_loss_tracking_per_pixel) forms the per-pixel residual; losses.get_loss_tracking_stacked
-    gives the RGB-D objective."""
+    gives the RGB-D objective.
+    num_pixels = K > 0 (or `pixel_indices`: K flat pixel indices to replay): the gradient is the pixel-sampled
+    estimate of losses.sampled_tracking_surrogate (utils/slam_frontend.py:573-592), the K pixels drawn with
+    torch.multinomial(q, K, replacement=True, generator=generator) and returned in render_pkg["sample_indices"];
+    the loss returned stays the exact norm."""
     residual_fn = get_loss_tracking_per_pixel if residual_fn is None else residual_fn
     render_pkg = render(viewpoint, gaussians, pipe, background)
     res = residual_fn(config, render_pkg["render"], render_pkg["depth"], render_pkg["opacity"], viewpoint)
     # the reference's best-iterate criterion: ||residual||_1 before Huber (slam_frontend.py:510)
     render_pkg["tracking_l1"] = res.detach().abs().sum()
     delta, p = tracking_norm(config)
-    if delta > 0:
-        res = HuberLoss.apply(res, delta)
-    loss = torch.norm(res.flatten(), p=p)
     pose_optimizer.zero_grad()
-    loss.backward()
+    if pixel_indices is not None or num_pixels > 0:
+        if pixel_indices is None:
+            with torch.no_grad():
+                v = res.detach().reshape(res.shape[0], -1).abs().sum(0) + 1e-8
+                pixel_indices = torch.multinomial(v / v.sum(), int(num_pixels), replacement=True, generator=generator)
+        render_pkg["sample_indices"] = pixel_indices
+        surrogate, loss = sampled_tracking_surrogate(res, pixel_indices, delta, p)
+        surrogate.backward()
+    else:
+        if delta > 0:
+            res = HuberLoss.apply(res, delta)
+        loss = torch.norm(res.flatten(), p=p)
+        loss.backward()
     with torch.no_grad():
         pose_optimizer.step()
         render_pkg["tracking_step_norm"] = torch.cat([viewpoint.cam_trans_delta, viewpoint.cam_rot_delta]).norm()
@@ -290,7 +312,7 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
                 use_first_order_best=True, use_best_loss=True, pipe=Pipe, config=DEFAULT_CONFIG,
                 stack_dim=16, sketch_dim=64, initial_lambda=1e-3, min_lambda=1e-6, max_lambda=1e7,
                 increase_factor=5.0, decrease_factor=5.0, second_order_converged_threshold=1e-5,
-                generator=None, fused=False, fsa_fn=None, repeat_dim=1, trace=None, residual_fn=None):
+                generator=None, fused=False, fsa_fn=None, repeat_dim=1, trace=None, residual_fn=None, num_pixels=-1):
     """The reference's tracking loop for one frame, reference-shaped Python on the HIP rasteriser
     (slam_frontend.py:455-822 with override_mode "none"): first-order iterations (Adam on the pose
     deltas and the exposure; a converged one leaves the whole loop, :623-626), then sketched LM
@@ -301,9 +323,11 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
     Returns (render_pkg, best_l1, best_iteration, iterations).  `fsa_fn(i)` may supply the sketch
     arguments of second-order iteration i (tests: the native tracker's partitions).  `trace` (a list)
     receives per iteration (L1 of its render, |step| it took, converged).  `residual_fn`: the per-pixel residual of
-    both orders (default get_loss_tracking_per_pixel; losses.get_loss_tracking_stacked for RGB-D, non-fused only)."""
-    if fused and residual_fn is not None:
-        raise ValueError("residual_fn needs the autograd first-order step (fused=False)")
+    both orders (default get_loss_tracking_per_pixel; losses.get_loss_tracking_stacked for RGB-D, non-fused only).
+    `num_pixels` > 0: the pixel-sampled first-order gradient (tracking_step_first_order, draws from `generator`);
+    second-order iterations are unaffected, as in the reference."""
+    if fused and (residual_fn is not None or num_pixels > 0):
+        raise ValueError("residual_fn / num_pixels need the autograd first-order step (fused=False)")
     if fused:
         from .tracking_fused import FusedPoseOptimizer
         lr = config["Training"]["lr"]
@@ -331,7 +355,10 @@ def track_frame(viewpoint, gaussians, background, first_order_iters=40, second_o
             best_state.assign(viewpoint)
         state = TempCamera(viewpoint)            # the state this iteration renders
         if not second:
-            if residual_fn is None:
+            if num_pixels > 0:
+                _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config, residual_fn=residual_fn,
+                                         num_pixels=num_pixels, generator=generator)
+            elif residual_fn is None:
                 _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config)
             else:
                 _, converged, pkg = step(viewpoint, gaussians, opt, background, pipe, config, residual_fn=residual_fn)

@@ -138,11 +138,13 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  init_iters: int = 1050, mapping_iters: int = 150, first_order_iters: int = 40,
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
-                 alpha: float = 0.95):
+                 alpha: float = 0.95, num_pixels: int = -1):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
-    the stacked RGB-D objective against its depth (NativeTracker(gt_depth=..., alpha=alpha))."""
+    the stacked RGB-D objective against its depth (NativeTracker(gt_depth=..., alpha=alpha)).  `num_pixels` > 0: the
+    first-order tracking iterations take the pixel-sampled gradient (NativeTracker(num_pixels=...); see
+    slam_loops.sampled_num_pixels for reading it from a config)."""
     if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
         raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
     H, W = cam.H, cam.W
@@ -188,7 +190,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         vp = camera(fr, cams[k - 1].T.detach().clone())           # previous pose (:358-362)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
-        trk = NativeTracker(vp, gm, bg, gt_depth=fr.depth if rgbd_tracking else None, alpha=alpha)
+        trk = NativeTracker(vp, gm, bg, gt_depth=fr.depth if rgbd_tracking else None, alpha=alpha,
+                            num_pixels=num_pixels, sample_seed=seed + k)
         if second_order_iters > 0:
             trk.enable_second_order(stack_dim=16, sketch_dim=64, initial_lambda=1e-3, seed=seed + k)
         # one frame of the reference's loop incl. its best-iterate bookkeeping (slam_frontend.py:455-822;

@@ -32,7 +32,8 @@ class NativeTracker:
 
     def __init__(self, viewpoint, gaussians, background, huber_delta=0.01, lr_rot=0.003,
                  lr_trans=0.001, lr_a=0.02, lr_b=0.02, betas=(0.9, 0.999), eps=1e-8,
-                 converged_threshold=1e-4, capacity_margin=1.5, pnorm=2.0, gt_depth=None, alpha=0.95):
+                 converged_threshold=1e-4, capacity_margin=1.5, pnorm=2.0, gt_depth=None, alpha=0.95, num_pixels=-1,
+                 sample_seed=0):
         # (huber_delta, pnorm) as slam_loops.tracking_norm(config) returns them: the reference's first-order
         # objective is Huber + L2 when RGN.use_huber, else the RGN.pnorm-norm without Huber (huber_delta = 0),
         # slam_frontend.py:596-600.  p = 1 and p = 2 ride in the forward blend's epilogue, any other p >= 1
@@ -40,6 +41,9 @@ class NativeTracker:
         # gt_depth ([H,W] or [1,H,W] sensor depth): RGB-D tracking - the objective is the stacked residual of
         # losses.get_loss_tracking_stacked (colour rows times `alpha`, the masked depth row times 1 - alpha) in every
         # first- and second-order iteration (the *_rgbd entry points); None keeps the monocular launch sequence.
+        # num_pixels = K > 0 (RGN.first_order.num_pixels, slam_loops.sampled_num_pixels): every first-order step() takes
+        # the pixel-sampled gradient of K pixels (mgs_tracking_iteration_sampled; DESIGN.md "Pixel-sampled first-order
+        # tracking"), drawn on the device with the key (sample_seed, sampled iteration); <= 0 keeps the dense step.
         vp = viewpoint
         dev = vp.T.device
         if dev.type != "cuda":
@@ -149,6 +153,21 @@ class NativeTracker:
         self.t = 0
         self._matrices_fresh = False
         self._T_ptr = vp.T.data_ptr()
+        self.num_pixels = int(num_pixels)
+        self.sample_seed = int(sample_seed)
+        self.sample_t = 0                  # sampled iterations enqueued (the draw's counter; not reset per frame)
+        self.sample_args = None
+        self.last_sample_indices = None
+        if self.num_pixels > 0:
+            if self.num_pixels > _cabi.TRACK_SAMPLE_MAX:
+                raise ValueError(f"num_pixels must be <= {_cabi.TRACK_SAMPLE_MAX}, got {self.num_pixels}")
+            nbytes = int(lib.mgs_tracking_sample_scratch_bytes(C.byref(shape), self.num_pixels))
+            self.sample_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)
+            self.last_sample_indices = torch.zeros(self.num_pixels, dtype=torch.int32, device=dev)
+            sa = _cabi.TrackingSampleArgs()
+            sa.num_samples = self.num_pixels
+            sa.indices, sa.scratch = self.last_sample_indices.data_ptr(), self.sample_scratch.data_ptr()
+            self.sample_args = sa
         self._d_max.zero_()
 
     def _stream(self):
@@ -254,8 +273,20 @@ class NativeTracker:
     def invalidate_matrices(self):
         self._matrices_fresh = False
 
-    def step(self):
-        """Enqueue one iteration; returns the device convergence flag (int32[1])."""
+    def sample_key(self, t=None):
+        """64-bit key of the draw of sampled iteration t (default: the next one), from (sample_seed, t)."""
+        t = self.sample_t + 1 if t is None else int(t)
+        return (self.sample_seed * 0x9E3779B97F4A7C15 + t) & 0xFFFFFFFFFFFFFFFF
+
+    def step(self, replay_indices=None, grad_out=None):
+        """Enqueue one iteration; returns the device convergence flag (int32[1]).  With num_pixels > 0 the gradient is
+        the pixel-sampled estimate and `last_sample_indices` (int32[K], device, tile order) holds the draw;
+        `replay_indices` (int32[K] on the device, tests) replaces the draw, `grad_out` (float[8] on the device) receives
+        the estimate before its Phi^(1-p) factor: d tau ([rho; theta]), d/da, d/db."""
+        if self.num_pixels > 0:
+            return self._step_sampled(replay_indices, grad_out)
+        if replay_indices is not None or grad_out is not None:
+            raise ValueError("replay_indices / grad_out need a tracker built with num_pixels > 0")
         self._sync_pose_pointer()
         self.t += 1
         self.args.adam.step = self.t
@@ -270,6 +301,28 @@ class NativeTracker:
                                                                 self._stream()),
                         "mgs_tracking_iteration_rgbd")
         self._matrices_fresh = True      # the Adam kernel wrote the matrices of the updated pose
+        return self.converged
+
+    def _step_sampled(self, replay_indices, grad_out):
+        self._sync_pose_pointer()
+        self.t += 1
+        self.sample_t += 1
+        self.args.adam.step = self.t
+        self.args.fwd.big_tile_pass = -1 if 0 < int(self._host_D[1]) <= 900 else 0
+        self.args.camera_matrices_valid = 1 if self._matrices_fresh else 0
+        sa = self.sample_args
+        sa.key = self.sample_key(self.sample_t)
+        for t, n in ((replay_indices, self.num_pixels), (grad_out, 8)):
+            if t is not None and not (t.is_cuda and t.is_contiguous() and t.numel() == n):
+                raise ValueError("replay_indices / grad_out must be contiguous device tensors of K / 8 elements")
+        if replay_indices is not None and replay_indices.dtype != torch.int32:
+            raise ValueError("replay_indices must be int32")
+        sa.replay_indices = None if replay_indices is None else replay_indices.data_ptr()
+        sa.grad_out = None if grad_out is None else grad_out.data_ptr()
+        depth = None if self.depth_args is None else C.byref(self.depth_args)
+        _cabi.check(_cabi.lib().mgs_tracking_iteration_sampled(C.byref(self.args), depth, C.byref(sa), self._stream()),
+                    "mgs_tracking_iteration_sampled")
+        self._matrices_fresh = True
         return self.converged
 
     @property
@@ -371,7 +424,8 @@ class NativeTracker:
         vp = self.vp
         keep = dict(T=vp.T.detach().clone(), a=vp.exposure_a.detach().clone(), b=vp.exposure_b.detach().clone(),
                     rot=vp.cam_rot_delta.detach().clone(), trans=vp.cam_trans_delta.detach().clone(),
-                    m=self.exp_avg.clone(), v=self.exp_avg_sq.clone(), t=self.t, best=self.best.clone())
+                    m=self.exp_avg.clone(), v=self.exp_avg_sq.clone(), t=self.t, best=self.best.clone(),
+                    sample_t=self.sample_t)
         if hasattr(self, "lm_state"):
             keep["lm"], keep["so_t"] = self.lm_state.clone(), self.so_t
         return keep
@@ -388,6 +442,7 @@ class NativeTracker:
                 self.lm_state.copy_(keep["lm"])
                 self.so_t = keep["so_t"]
         self.t = keep["t"]
+        self.sample_t = keep["sample_t"]
         self.converged.zero_()
         self._matrices_fresh = False
 
