@@ -204,7 +204,8 @@ int32_t mgs_abi_version(void);
  * 11 = mgs_adam_group, 12 = mgs_map_plan_args, 13 = mgs_gather_tensor, 14 = mgs_map_gather_args,
  * 15 = mgs_map_accum_args, 16 = mgs_map_activate_args, 17 = mgs_mapping_view_args,
  * 18 = mgs_map_finish_args, 19 = mgs_map_append_args, 20 = mgs_ssim_loss_args,
- * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args, 23 = mgs_tracking_sample_args);
+ * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args, 23 = mgs_tracking_sample_args,
+ * 24 = mgs_keyframe_args);
  * -1 for an unknown index.  Lets a foreign-language binding verify its struct mirrors. */
 int32_t mgs_struct_size(int32_t which);
 const char* mgs_status_string(int32_t status);
@@ -642,6 +643,67 @@ uint64_t mgs_tracking_sample_scratch_bytes(const mgs_raster_shape* shape, int32_
  * depth == NULL: monocular; else the stacked RGB-D residual of mgs_tracking_iteration_rgbd.  Any p >= 1. */
 int32_t mgs_tracking_iteration_sampled(const mgs_tracking_iter_args* args, const mgs_tracking_depth_args* depth,
                                        const mgs_tracking_sample_args* sample, void* stream);
+
+/* ---- keyframe selection and window management ("Keyframe policy on the device") ----------------------
+ * The reference frontend's per-frame decision (utils/slam_frontend.py: is_keyframe :1692-1720, add_to_window
+ * :1722-1783, the run loop :1914-1956) from the device-resident inputs, in three stream-ordered launches and with no
+ * host synchronisation:
+ *   1. median-depth radix pass 1 (bits 31..21) over the valid pixels (depth > 0 && opacity > 0.95) and the
+ *      covisibility counts |cur|, |row_w|, |cur & row_w| (cur = n_touched > 0, row_w = visibility[w] != 0);
+ *   2. radix pass 2 (bits 20..10) inside the selected bucket;
+ *   3. radix pass 3 (bits 9..0), then the workgroup that takes the last ticket selects the lower median
+ *      (rank (n - 1) / 2, torch.median's) and evaluates the decision into *result.
+ * All counting is integer: two calls give bit-identical records.  The overlap ratios are fp32 divisions of the exact
+ * counts (0 / 0 = NaN: compares false), dist is fp32 from T_cur * T_last^-1 (rigid inverse [R^T | -R^T t]), the
+ * eviction score takes fp32 norms and fp64 reciprocals / sums / products; ties go to the first position.
+ * The window is ordered newest first (window[0] = the last keyframe), as the reference's current_window. */
+#define MGS_KF_MAX_WINDOW 16
+typedef struct mgs_keyframe_args {
+  int32_t num_gaussians;           /* N >= 1 */
+  int32_t num_pixels;              /* H * W >= 1 */
+  int32_t window_len;              /* W, 1 .. MGS_KF_MAX_WINDOW (above: MGS_ERR_UNSUPPORTED) */
+  int32_t window_size;             /* Training.window_size >= 1 */
+  int32_t check_time;              /* (cur_frame_idx - window[0]) >= kf_interval */
+  int32_t initialized;             /* the frontend's flag (set once the window has been full; !monocular at start) */
+  int32_t monocular;
+  int32_t single_thread;           /* Dataset.single_thread: create_kf &= check_time */
+  float kf_translation, kf_min_translation, kf_overlap, kf_cutoff;
+  const int32_t* n_touched;        /* [N] current frame's render (tracking's best iterate) */
+  const float* depth;              /* [H*W] */
+  const float* opacity;            /* [H*W] */
+  const float* T_cur;              /* [4][4] row-major world-to-camera pose of the current frame */
+  const float* T_window[MGS_KF_MAX_WINDOW];            /* [4][4] per window keyframe */
+  const uint8_t* visibility[MGS_KF_MAX_WINDOW];        /* [N] per window keyframe: occ-aware visibility */
+  int64_t visibility_len[MGS_KF_MAX_WINDOW];           /* element count of each row: must equal N */
+  void* scratch;                   /* mgs_keyframe_scratch_bytes(N, H*W, W) bytes; zero-filled once before the first
+                                      call (every call leaves it as it found it) */
+  void* result;                    /* device mgs_keyframe_result */
+} mgs_keyframe_args;
+
+typedef struct mgs_keyframe_result {
+  int32_t create_kf;               /* the run loop's decision */
+  int32_t removed;                 /* window position of add_to_window's removed frame, -1 (only if create_kf) */
+  int32_t reset;                   /* monocular && !initialized && removed >= 0 */
+  int32_t n_valid;                 /* valid depth pixels */
+  int32_t removed_cutoff;          /* position dropped by the kf_cutoff rule (the last one at or below it), -1 */
+  int32_t removed_evict;           /* position evicted by the inverse-distance score, -1 */
+  int32_t n_cur;                   /* |cur| */
+  int32_t flags;                   /* bit 0 dist_check, bit 1 dist_check2, bit 2 is_keyframe() */
+  float median_depth;              /* NaN when n_valid == 0 */
+  float dist;                      /* |t(T_cur T_last^-1)| */
+  float overlap;                   /* |cur & row_0| / |cur | row_0| */
+  int32_t window_len;
+  float ss_ratio[MGS_KF_MAX_WINDOW];   /* |cur & row_w| / min(|cur|, |row_w|) */
+  int32_t n_row[MGS_KF_MAX_WINDOW];    /* |row_w| */
+  int32_t n_inter[MGS_KF_MAX_WINDOW];  /* |cur & row_w| */
+  double score[MGS_KF_MAX_WINDOW];     /* eviction score by window position; -1 where not a candidate */
+} mgs_keyframe_result;
+
+/* 0 for a bad size.  num_pixels = H * W, window_len = W. */
+uint64_t mgs_keyframe_scratch_bytes(int32_t num_gaussians, int32_t num_pixels, int32_t window_len);
+/* Every argument is checked before anything is launched: a null pointer, a non-positive size or a row whose length is
+ * not N gives MGS_ERR_BAD_ARGUMENT, window_len > MGS_KF_MAX_WINDOW MGS_ERR_UNSUPPORTED. */
+int32_t mgs_keyframe_decide(const mgs_keyframe_args* args, void* stream);
 
 /* ---- map maintenance on the device ---------------------------------- */
 

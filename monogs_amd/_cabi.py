@@ -29,6 +29,7 @@ EXPORTS = (
     "mgs_ssim_loss_partial_count", "mgs_ssim_loss", "mgs_refine_view_iteration",
     "mgs_tracking_iteration_rgbd", "mgs_tracking_iteration_second_order_rgbd", "mgs_tracking_loss_rgbd_fused",
     "mgs_sketch_residual_rgbd", "mgs_tracking_sample_scratch_bytes", "mgs_tracking_iteration_sampled",
+    "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -217,6 +218,25 @@ class TrackingSampleArgs(C.Structure):
 
 TRACK_SAMPLE_MAX = 65536
 
+KF_MAX_WINDOW = 16
+
+
+class KeyframeArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_gaussians", "num_pixels", "window_len", "window_size", "check_time",
+                                          "initialized", "monocular", "single_thread")]
+                + [(n, C.c_float) for n in ("kf_translation", "kf_min_translation", "kf_overlap", "kf_cutoff")]
+                + [(n, _fp) for n in ("n_touched", "depth", "opacity", "T_cur")]
+                + [("T_window", _fp * KF_MAX_WINDOW), ("visibility", _fp * KF_MAX_WINDOW),
+                   ("visibility_len", C.c_int64 * KF_MAX_WINDOW), ("scratch", _fp), ("result", _fp)])
+
+
+class KeyframeResult(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("create_kf", "removed", "reset", "n_valid", "removed_cutoff",
+                                          "removed_evict", "n_cur", "flags")]
+                + [("median_depth", C.c_float), ("dist", C.c_float), ("overlap", C.c_float), ("window_len", C.c_int32),
+                   ("ss_ratio", C.c_float * KF_MAX_WINDOW), ("n_row", C.c_int32 * KF_MAX_WINDOW),
+                   ("n_inter", C.c_int32 * KF_MAX_WINDOW), ("score", C.c_double * KF_MAX_WINDOW)])
+
 _lib = None
 
 
@@ -336,6 +356,10 @@ def lib():
     L.mgs_tracking_iteration_sampled.restype = C.c_int32
     L.mgs_tracking_iteration_sampled.argtypes = [C.POINTER(TrackingIterArgs), _dp, C.POINTER(TrackingSampleArgs),
                                                  C.c_void_p]
+    L.mgs_keyframe_scratch_bytes.restype = C.c_uint64
+    L.mgs_keyframe_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mgs_keyframe_decide.restype = C.c_int32
+    L.mgs_keyframe_decide.argtypes = [C.POINTER(KeyframeArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")
@@ -349,7 +373,7 @@ def struct_mirrors():
             LMStepArgs, TrackingLossArgs, TrackingIterArgs, SketchResidualArgs, TrackingSOArgs,
             AdamGroup, MapPlanArgs, GatherTensor, MapGatherArgs, MapAccumArgs, MapActivateArgs,
             MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs, TrackingDepthArgs,
-            TrackingSampleArgs]
+            TrackingSampleArgs, KeyframeArgs]
 
 
 def check(status: int, what: str) -> None:

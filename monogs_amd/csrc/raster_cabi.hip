@@ -137,6 +137,7 @@ int32_t mgs_struct_size(int32_t which) {
     case 21: return (int32_t)sizeof(mgs_refine_view_args);
     case 22: return (int32_t)sizeof(mgs_tracking_depth_args);
     case 23: return (int32_t)sizeof(mgs_tracking_sample_args);
+    case 24: return (int32_t)sizeof(mgs_keyframe_args);
     default: return -1;
   }
 }
@@ -425,6 +426,33 @@ int32_t mgs_tracking_iteration_sampled(const mgs_tracking_iter_args* args, const
                                        const mgs_tracking_sample_args* sample, void* stream) {
   if (depth && !depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
   return tracking_iteration_sampled_impl(args, depth, sample, stream);
+}
+
+}  // extern "C"
+
+// Keyframe policy (keyframe_policy.hip): every argument is checked here, before anything is launched.
+static int32_t keyframe_args_status(const mgs_keyframe_args* a) {
+  if (!a || a->num_gaussians < 1 || a->num_pixels < 1 || a->window_len < 1 || a->window_size < 1)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (a->window_len > MGS_KF_MAX_WINDOW) return MGS_ERR_UNSUPPORTED;
+  if (!a->n_touched || !a->depth || !a->opacity || !a->T_cur || !a->scratch || !a->result) return MGS_ERR_BAD_ARGUMENT;
+  for (int w = 0; w < a->window_len; w++)
+    if (!a->T_window[w] || !a->visibility[w] || a->visibility_len[w] != (int64_t)a->num_gaussians)
+      return MGS_ERR_BAD_ARGUMENT;
+  return MGS_OK;
+}
+
+extern "C" {
+
+uint64_t mgs_keyframe_scratch_bytes(int32_t num_gaussians, int32_t num_pixels, int32_t window_len) {
+  if (num_gaussians < 1 || num_pixels < 1 || window_len < 1 || window_len > MGS_KF_MAX_WINDOW) return 0;
+  return kf_layout(num_gaussians, num_pixels).bytes;
+}
+
+int32_t mgs_keyframe_decide(const mgs_keyframe_args* args, void* stream) {
+  const int32_t rc = keyframe_args_status(args);
+  if (rc != MGS_OK) return rc;
+  return launch_keyframe_decide(*args, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -17,9 +17,10 @@ What is mirrored (/root/reference utils/slam_frontend.py, slam_backend.py):
   keyframe insertion   add_new_keyframe :183-230 (monocular: rendered depth, outliers replaced by the
                        median, noise), backend "keyframe" message :427-493 (extend_from_pcd_seq, new
                        keyframe optimiser, map(iters), map(prune=True))
-What is NOT the reference's: the keyframe POLICY (is_keyframe / add_to_window :1692-1783 are pure
-policy, out of scope): a keyframe every `kf_interval` frames, window = the newest `window_size`
-keyframes.
+  keyframe policy      by default NOT the reference's: a keyframe every `kf_interval` frames, window =
+                       the newest `window_size` keyframes.  With keyframe_policy=KeyframePolicy(...) the
+                       reference's: is_keyframe / add_to_window / the run loop's decision :1692-1783,
+                       :1914-1956 (keyframe_policy.py), including the monocular reset :1942-1950.
 """
 from __future__ import annotations
 
@@ -32,6 +33,7 @@ import torch
 
 from . import synthetic as S
 from .gaussian_model import GaussianModel
+from .keyframe_policy import KeyframePolicy
 from .mapping_native import NativeMapper
 from .pose import SE3_exp
 from .slam_loops import GaussianParams, Pipe, ViewCamera
@@ -138,15 +140,24 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  init_iters: int = 1050, mapping_iters: int = 150, first_order_iters: int = 40,
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
-                 alpha: float = 0.95, num_pixels: int = -1):
+                 alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
     the stacked RGB-D objective against its depth (NativeTracker(gt_depth=..., alpha=alpha)).  `num_pixels` > 0: the
     first-order tracking iterations take the pixel-sampled gradient (NativeTracker(num_pixels=...); see
-    slam_loops.sampled_num_pixels for reading it from a config)."""
+    slam_loops.sampled_num_pixels for reading it from a config).  `keyframe_policy`: None inserts a keyframe every
+    `kf_interval` frames into a FIFO window; a KeyframePolicy decides every tracked frame the reference's way
+    (keyframe_policy.py; its window_size and kf_interval are used), and a monocular reset re-initialises a fresh map
+    on the frame that triggered it, at its ground-truth pose - the reference's loop reads that frame again
+    (:1942-1950, initialize :236-252).  The result then also holds `decisions` (one per tracked frame), `windows`
+    (the window after each tracked frame) and `resets` (the frames that re-initialised the map)."""
     if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
         raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
+    policy = keyframe_policy
+    if policy is not None:
+        window_size, kf_interval = policy.window_size, policy.kf_interval
+        policy.reset_state()
     H, W = cam.H, cam.W
     fovx, fovy = 2 * math.atan(cam.tanfovx), 2 * math.atan(cam.tanfovy)
     gen = torch.Generator(device=dev).manual_seed(seed)
@@ -185,6 +196,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     window = [0]
     kf_ids = [0]
     last_kf = 0
+    decisions, windows, resets = [], [], []
     for k in range(1, len(frames)):
         fr = frames[k]
         vp = camera(fr, cams[k - 1].T.detach().clone())           # previous pose (:358-362)
@@ -203,12 +215,40 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         t_track += time.perf_counter() - t0
         n_track_iters += it
         cams[k] = vp
-        if k - last_kf >= kf_interval:
+        if policy is None:
+            create_kf = k - last_kf >= kf_interval
+            new_window = ([k] + window)[:window_size]
+        else:
+            dec = policy.decide(k, cams, window, trk, mapper.occ_aware_visibility)
+            decisions.append(dec)
+            create_kf, new_window = dec.create_kf, dec.window
+            if dec.reset:
+                # frontend.initialize + BackEnd.reset: a fresh map from this frame at its ground-truth pose
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                resets.append(k)
+                policy.reset_state()
+                gm = GaussianModel(0, config=cfg, device=dev)
+                gm.init_lr(6.0)
+                gm.training_setup()
+                mapper = NativeMapper(gm, bg, config=cfg, cameras_extent=6.0, seed=seed)
+                cams[k] = camera(fr, fr.T_gt.to(dev).float().clone())
+                dk = keyframe_depth(fr.image, None, None, fr.depth if sensor_depth else None, gen)
+                gm.extend_from_pcd_seq(cams[k], kf_id=k, init=True, depthmap=dk, generator=gen)
+                mapper.add_keyframe(k, cams[k])
+                mapper.set_window([k])
+                mapper.initialize_map(k, iters=init_iters)
+                torch.cuda.synchronize()
+                t_init += time.perf_counter() - t0
+                window, kf_ids, last_kf = [k], [k], k
+                windows.append(list(window))
+                continue
+        if create_kf:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             depth_map = keyframe_depth(fr.image, trk.depth, trk.opacity, fr.depth if sensor_depth else None, gen)
             gm.extend_from_pcd_seq(vp, kf_id=k, init=False, depthmap=depth_map, generator=gen)
-            window = ([k] + window)[:window_size]
+            window = new_window
             kf_ids.append(k)
             last_kf = k
             mapper.add_keyframe(k, vp)
@@ -224,10 +264,12 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             n_map_views += iters * (len(window) + min(2, len(kf_ids) - len(window)))
             if log:
                 log(f"keyframe {k}: window {window}, {len(gm)} Gaussians, loss {float(mapper.last_loss):.4f}")
+        windows.append(list(window))
     ok = mapper.check_capacity()
     return {"cameras": cams, "kf_ids": kf_ids, "gaussians": gm, "mapper": mapper, "t_init": t_init,
             "t_track": t_track, "t_map": t_map, "n_track_iters": n_track_iters, "n_map_iters": n_map_iters,
-            "n_map_views": n_map_views, "capacity_ok": ok, "frames_tracked": len(frames) - 1}
+            "n_map_views": n_map_views, "capacity_ok": ok, "frames_tracked": len(frames) - 1,
+            "decisions": decisions, "windows": windows, "resets": resets}
 
 
 def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
