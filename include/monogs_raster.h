@@ -205,7 +205,7 @@ int32_t mgs_abi_version(void);
  * 15 = mgs_map_accum_args, 16 = mgs_map_activate_args, 17 = mgs_mapping_view_args,
  * 18 = mgs_map_finish_args, 19 = mgs_map_append_args, 20 = mgs_ssim_loss_args,
  * 21 = mgs_refine_view_args, 22 = mgs_tracking_depth_args, 23 = mgs_tracking_sample_args,
- * 24 = mgs_keyframe_args);
+ * 24 = mgs_keyframe_args, 25 = mgs_keyframe_seed_args);
  * -1 for an unknown index.  Lets a foreign-language binding verify its struct mirrors. */
 int32_t mgs_struct_size(int32_t which);
 const char* mgs_status_string(int32_t status);
@@ -704,6 +704,79 @@ uint64_t mgs_keyframe_scratch_bytes(int32_t num_gaussians, int32_t num_pixels, i
 /* Every argument is checked before anything is launched: a null pointer, a non-positive size or a row whose length is
  * not N gives MGS_ERR_BAD_ARGUMENT, window_len > MGS_KF_MAX_WINDOW MGS_ERR_UNSUPPORTED. */
 int32_t mgs_keyframe_decide(const mgs_keyframe_args* args, void* stream);
+
+/* ---- keyframe seeding ("Keyframe seeding on the device") ----------------------------------------------
+ * From a tracked frame to the rows of its new Gaussians: the reference frontend's depth prior (add_new_keyframe,
+ * utils/slam_frontend.py:183-234), the adaptive point size (np.median of the prepared depth map,
+ * gaussian_model.py:143), a random K-subset of the valid pixels, their back-projection and colour
+ * (create_pcd_from_image_and_depth :137-205) and the k-nn scale, stream-ordered, with ONE host read (the record, which
+ * carries the row count the k-nn launcher and the caller's append need).
+ *   mode 0  monocular, rendered depth: valid = depth > 0 && opacity > 0.95 && valid_rgb; med = lower median of the
+ *           valid depths (torch.median's element); std = their unbiased standard deviation (fp64 sums over a fixed
+ *           tree, rounded once); bad = d > med + std || d < med - std || !valid; d = bad ? med : d;
+ *           d += noise * (bad ? 0.5 std : 0.2 std).  Fewer than two valid pixels: d = 2 everywhere.
+ *   mode 1  monocular, first keyframe / reset: d = 2 + 0.3 noise.        mode 2  d = depth (the sensor's).
+ * Then d = 0 where d is not finite and, in modes 0 and 2, where !valid_rgb (valid_rgb = (r + g) + b >
+ * rgb_boundary_threshold; the reference's first-keyframe branch does not apply that mask).
+ * point_size = adaptive_pointsize ? min(0.05, point_size * median_all) : point_size, median_all = NumPy's median of
+ * all H*W values of d (zeros included; the mean of the two middle order statistics when H*W is even).
+ * n = #{0 < d <= depth_trunc}, K = floor(n / downsample); every such pixel has a 32-bit key (keys[i], or drawn) and
+ * the K smallest (key, pixel index) pairs are kept, in ascending pixel order.  Row p of the outputs, pixel (u, v),
+ * z = d: xyz = R^T (((u - cx) z / fx, (v - cy) z / fy, z) - t); features_dc = RGB2SH(floor(clamp((|a| + eps) image
+ * + b, 0, 1) * 255) / 255); rots = (1, 0, 0, 0); opacity_logit = 0; log_scales = log(sqrt(max(dist2, 1e-7) *
+ * point_size)), dist2 = mgs_knn_dist2 of xyz[0:K].
+ * noise == NULL / keys == NULL: the values are drawn from Philox-4x32-10 keyed by `seed` with the counter
+ * (pixel index, 0, stream id, 0), stream 0 = noise (Box-Muller of the first two words), stream 1 = keys (first word).
+ * No float atomics: two calls with the same inputs give bit-identical outputs. */
+typedef struct mgs_keyframe_seed_result {
+  int32_t num_points;              /* K: rows written */
+  int32_t n_valid;                 /* mode 0: pixels behind median_depth / std_depth; otherwise 0 */
+  int32_t n_outliers;              /* mode 0: pixels whose depth was replaced by the median; otherwise 0 */
+  int32_t n_depth;                 /* n = #{0 < d <= depth_trunc} */
+  float median_depth, std_depth;   /* mode 0 (NaN with fewer than 1 / 2 valid pixels); otherwise NaN */
+  float median_all;                /* np.median of the prepared depth map */
+  float point_size;                /* the value behind log_scales */
+} mgs_keyframe_seed_result;
+
+typedef struct mgs_keyframe_seed_args {
+  int32_t width, height;
+  int32_t row_capacity;            /* rows of every output; at least floor(width * height / downsample) */
+  int32_t mode;                    /* 0, 1, 2 (above) */
+  int32_t adaptive_pointsize, isotropic;   /* isotropic: log_scales is [P,1], else [P,3] (the value repeated) */
+  float fx, fy, cx, cy;
+  float rgb_boundary_threshold;
+  float downsample;                /* >= 1 (the reference keeps 1 / downsample of the points) */
+  float depth_trunc;               /* 100 in the reference */
+  float exposure_eps;
+  double point_size;
+  uint64_t seed;
+  const float* image;              /* [3][H][W] */
+  const float* depth;              /* [H*W]; mode 0: rendered, mode 2: sensor; mode 1: unused (may be NULL) */
+  const float* opacity;            /* [H*W]; mode 0 only */
+  const float* T;                  /* device [4][4] row-major world-to-camera */
+  const float* exposure_a;         /* device scalars */
+  const float* exposure_b;
+  const float* noise;              /* [H*W] replay of the normal draws, or NULL */
+  const uint32_t* keys;            /* [H*W] replay of the sampling keys, or NULL */
+  float* xyz;                      /* [P][3] */
+  float* features_dc;              /* [P][3] */
+  float* log_scales;               /* [P][1 or 3] */
+  float* rots;                     /* [P][4] */
+  float* opacity_logit;            /* [P][1] */
+  int32_t* pixel_index;            /* [P] flat index of each row's pixel (ascending), or NULL */
+  float* depth_out;                /* [H*W] the prepared depth map, or NULL */
+  void* scratch;                   /* mgs_keyframe_seed_scratch_bytes(H*W, row_capacity) bytes, 16-byte aligned */
+  void* result;                    /* device mgs_keyframe_seed_result */
+  mgs_keyframe_seed_result* result_host;   /* host copy of the record, valid on return */
+} mgs_keyframe_seed_args;
+
+/* 0 for non-positive sizes. */
+uint64_t mgs_keyframe_seed_scratch_bytes(int32_t num_pixels, int32_t row_capacity);
+/* Every argument is checked before anything is launched or written: a null pointer (depth in modes 0 / 2, opacity in
+ * mode 0 and every other pointer not marked optional), a non-positive size, downsample < 1 (or NaN), an unknown mode,
+ * a scratch address that is not 16-byte aligned or row_capacity < floor(width * height / downsample) give
+ * MGS_ERR_BAD_ARGUMENT.  Synchronises `stream` once. */
+int32_t mgs_keyframe_seed(const mgs_keyframe_seed_args* args, void* stream);
 
 /* ---- map maintenance on the device ---------------------------------- */
 

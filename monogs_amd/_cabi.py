@@ -29,7 +29,7 @@ EXPORTS = (
     "mgs_ssim_loss_partial_count", "mgs_ssim_loss", "mgs_refine_view_iteration",
     "mgs_tracking_iteration_rgbd", "mgs_tracking_iteration_second_order_rgbd", "mgs_tracking_loss_rgbd_fused",
     "mgs_sketch_residual_rgbd", "mgs_tracking_sample_scratch_bytes", "mgs_tracking_iteration_sampled",
-    "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide",
+    "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide", "mgs_keyframe_seed_scratch_bytes", "mgs_keyframe_seed",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -237,6 +237,22 @@ class KeyframeResult(C.Structure):
                    ("ss_ratio", C.c_float * KF_MAX_WINDOW), ("n_row", C.c_int32 * KF_MAX_WINDOW),
                    ("n_inter", C.c_int32 * KF_MAX_WINDOW), ("score", C.c_double * KF_MAX_WINDOW)])
 
+class KeyframeSeedResult(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_points", "n_valid", "n_outliers", "n_depth")]
+                + [(n, C.c_float) for n in ("median_depth", "std_depth", "median_all", "point_size")])
+
+
+class KeyframeSeedArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "row_capacity", "mode", "adaptive_pointsize", "isotropic")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "rgb_boundary_threshold", "downsample",
+                                            "depth_trunc", "exposure_eps")]
+                + [("point_size", C.c_double), ("seed", C.c_uint64)]
+                + [(n, _fp) for n in ("image", "depth", "opacity", "T", "exposure_a", "exposure_b", "noise", "keys",
+                                      "xyz", "features_dc", "log_scales", "rots", "opacity_logit", "pixel_index",
+                                      "depth_out", "scratch", "result")]
+                + [("result_host", C.POINTER(KeyframeSeedResult))])
+
+
 _lib = None
 
 
@@ -360,6 +376,10 @@ def lib():
     L.mgs_keyframe_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
     L.mgs_keyframe_decide.restype = C.c_int32
     L.mgs_keyframe_decide.argtypes = [C.POINTER(KeyframeArgs), C.c_void_p]
+    L.mgs_keyframe_seed_scratch_bytes.restype = C.c_uint64
+    L.mgs_keyframe_seed_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.mgs_keyframe_seed.restype = C.c_int32
+    L.mgs_keyframe_seed.argtypes = [C.POINTER(KeyframeSeedArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")
@@ -373,7 +393,7 @@ def struct_mirrors():
             LMStepArgs, TrackingLossArgs, TrackingIterArgs, SketchResidualArgs, TrackingSOArgs,
             AdamGroup, MapPlanArgs, GatherTensor, MapGatherArgs, MapAccumArgs, MapActivateArgs,
             MappingViewArgs, MapFinishArgs, MapAppendArgs, SsimLossArgs, RefineViewArgs, TrackingDepthArgs,
-            TrackingSampleArgs, KeyframeArgs]
+            TrackingSampleArgs, KeyframeArgs, KeyframeSeedArgs]
 
 
 def check(status: int, what: str) -> None:

@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "launch.h"
+#include "radix_select.h"
 #include "raster_kernels.h"
 
 namespace mgs {
@@ -30,45 +31,6 @@ constexpr int kHist1 = 2048, kHist2 = 2048, kHist3 = 1024;
 constexpr int kKfCounts = 1 + 2 * MGS_KF_MAX_WINDOW;   // |cur|, |row_w| x 16, |cur & row_w| x 16
 
 __device__ __forceinline__ bool depth_valid(float d, float o) { return d > 0.f && o > 0.95f; }
-
-// Block-wide search of `hist` (nb = 8 * 256 or 4 * 256 buckets) for the bucket holding rank k (k < 0: the lower-median
-// rank of the histogram's own total).  s_out = {bucket or -1, rank inside it, total}.  All threads call it.
-template <int PER>
-__device__ void block_select(const int* hist, int k, int* s_scan, int* s_out) {
-  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-  int h[PER];
-  int local = 0;
-#pragma unroll
-  for (int j = 0; j < PER; j++) {
-    h[j] = __hip_atomic_load(&hist[tid * PER + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    local += h[j];
-  }
-  int incl = local;   // inclusive scan inside the wave
-  for (int off = 1; off < 64; off <<= 1) {
-    const int v = __shfl_up(incl, off);
-    if (lane >= off) incl += v;
-  }
-  if (lane == 63) s_scan[wv] = incl;
-  __syncthreads();
-  int base = 0, total = 0;
-  for (int w = 0; w < kKfThreads / 64; w++) {
-    if (w < wv) base += s_scan[w];
-    total += s_scan[w];
-  }
-  if (k < 0) k = (total - 1) / 2;   // total == 0: k = 0, no bucket holds it
-  const int excl = base + incl - local;
-  if (tid == 0) { s_out[0] = -1; s_out[1] = 0; s_out[2] = total; }
-  __syncthreads();
-  if (total > 0 && k >= excl && k < excl + local) {
-    int c = excl;
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-      if (k >= c && k < c + h[j]) { s_out[0] = tid * PER + j; s_out[1] = k - c; }
-      c += h[j];
-    }
-  }
-  __syncthreads();
-}
 
 // |translation of Ti Tj^-1|, both row-major world-to-camera rigid motions: Tj^-1 = [Rj^T | -Rj^T tj].
 __device__ float rel_translation_norm(const float* Ti, const float* Tj) {
@@ -236,11 +198,11 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
   unsigned prefix = 0;
   bool any = true;
   if (PASS >= 2) {
-    block_select<kHist1 / kKfThreads>(S.hist1, -1, s_scan, s_sel[0]);
+    block_select<kKfThreads, kHist1 / kKfThreads>(S.hist1, -1, s_scan, s_sel[0]);
     any = s_sel[0][0] >= 0;
     prefix = (unsigned)s_sel[0][0];
     if (PASS == 3 && any) {
-      block_select<kHist2 / kKfThreads>(S.hist2, s_sel[0][1], s_scan, s_sel[1]);
+      block_select<kKfThreads, kHist2 / kKfThreads>(S.hist2, s_sel[0][1], s_scan, s_sel[1]);
       prefix = prefix << 11 | (unsigned)s_sel[1][0];
     }
   }
@@ -306,7 +268,7 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
   const int n_valid = s_sel[0][2];
   float med = __uint_as_float(0x7fc00000u);   // NaN: torch.median of an empty selection
   if (any) {
-    block_select<kHist3 / kKfThreads>(S.hist3, s_sel[1][1], s_scan, s_sel[1]);
+    block_select<kKfThreads, kHist3 / kKfThreads>(S.hist3, s_sel[1][1], s_scan, s_sel[1]);
     med = __uint_as_float(prefix << 10 | (unsigned)s_sel[1][0]);
   }
   // count partials: thread t loads workgroup t's 33 ints (independent loads, bc <= 256), then wave and block sums

@@ -1,0 +1,72 @@
+// Rank selection over a device histogram, shared by the radix selects of keyframe_policy.hip (the median depth of
+// mgs_keyframe_decide) and keyframe_seed.hip (the depth prior's median, NumPy's median of the prepared depth map and
+// the K-th smallest sampling key of mgs_keyframe_seed).
+//
+// A select of 32-bit keys runs three histogram levels (bits 31..21, 20..10, 9..0: 2048 / 2048 / 1024 buckets); every
+// workgroup of the next level repeats the search of the previous level's histogram itself, so no grid-wide barrier
+// and no spinning is needed.  Positive fp32 values order like their uint32 bit patterns (+inf included);
+// float_order_key() extends that order to negative values.
+#pragma once
+#include <hip/hip_runtime.h>
+
+namespace mgs {
+
+constexpr int kRadixHist1 = 2048, kRadixHist2 = 2048, kRadixHist3 = 1024;
+
+// Block-wide search of `hist` (THREADS * PER buckets) for the bucket holding rank k = rank_of(total).  rank_of gets
+// the histogram's own total and returns the wanted rank, or a negative value for "none".
+// s_out = {bucket or -1, rank inside it, total}; s_scan holds THREADS / 64 ints.  All threads call it.
+template <int THREADS, int PER, class RankOf>
+__device__ void block_select_by(const int* hist, RankOf rank_of, int* s_scan, int* s_out) {
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int h[PER];
+  int local = 0;
+#pragma unroll
+  for (int j = 0; j < PER; j++) {
+    h[j] = __hip_atomic_load(&hist[tid * PER + j], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    local += h[j];
+  }
+  int incl = local;   // inclusive scan inside the wave
+  for (int off = 1; off < 64; off <<= 1) {
+    const int v = __shfl_up(incl, off);
+    if (lane >= off) incl += v;
+  }
+  if (lane == 63) s_scan[wv] = incl;
+  __syncthreads();
+  int base = 0, total = 0;
+  for (int w = 0; w < THREADS / 64; w++) {
+    if (w < wv) base += s_scan[w];
+    total += s_scan[w];
+  }
+  const int k = rank_of(total);
+  const int excl = base + incl - local;
+  if (tid == 0) { s_out[0] = -1; s_out[1] = 0; s_out[2] = total; }
+  __syncthreads();
+  if (total > 0 && k >= excl && k < excl + local) {
+    int c = excl;
+#pragma unroll
+    for (int j = 0; j < PER; j++) {
+      if (k >= c && k < c + h[j]) { s_out[0] = tid * PER + j; s_out[1] = k - c; }
+      c += h[j];
+    }
+  }
+  __syncthreads();
+}
+
+// Rank k, or (k < 0) the lower-median rank (total - 1) / 2 of the histogram's own total - torch.median's element.
+// total == 0: k = 0, no bucket holds it.
+template <int THREADS, int PER>
+__device__ void block_select(const int* hist, int k, int* s_scan, int* s_out) {
+  block_select_by<THREADS, PER>(hist, [k](int total) { return k < 0 ? (total - 1) / 2 : k; }, s_scan, s_out);
+}
+
+// uint32 keys in the order of the floats they came from (negative values below positive ones; -0 below +0).
+__device__ __forceinline__ unsigned float_order_key(float x) {
+  const unsigned b = __float_as_uint(x);
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float float_from_order_key(unsigned m) {
+  return __uint_as_float((m & 0x80000000u) ? (m & 0x7fffffffu) : ~m);
+}
+
+}  // namespace mgs

@@ -30,10 +30,8 @@ namespace mgs {
 int launch_forward_project(const KP& P, hipStream_t st);
 int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD = nullptr);
 int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_reduce, const SketchFuse* fuse);
-int launch_knn(const float* pts, int n, float* out, void* scratch, hipStream_t st);
 int launch_visibility(const int* n_touched, unsigned char* vis, int n, hipStream_t st);
 int launch_radii_fold(const int* radii, float* max_radii, int n, hipStream_t st);
-uint64_t knn_scratch_bytes(int n);
 }  // namespace mgs
 
 using namespace mgs;
@@ -138,6 +136,7 @@ int32_t mgs_struct_size(int32_t which) {
     case 22: return (int32_t)sizeof(mgs_tracking_depth_args);
     case 23: return (int32_t)sizeof(mgs_tracking_sample_args);
     case 24: return (int32_t)sizeof(mgs_keyframe_args);
+    case 25: return (int32_t)sizeof(mgs_keyframe_seed_args);
     default: return -1;
   }
 }
@@ -453,6 +452,36 @@ int32_t mgs_keyframe_decide(const mgs_keyframe_args* args, void* stream) {
   const int32_t rc = keyframe_args_status(args);
   if (rc != MGS_OK) return rc;
   return launch_keyframe_decide(*args, (hipStream_t)stream);
+}
+
+}  // extern "C"
+
+// Keyframe seeding (keyframe_seed.hip): likewise, every argument is checked before anything is launched or written.
+static int32_t keyframe_seed_args_status(const mgs_keyframe_seed_args* a) {
+  if (!a || a->width < 1 || a->height < 1 || a->row_capacity < 1 || (int64_t)a->width * a->height > 0x7fffffff)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (a->mode < 0 || a->mode > 2 || !(a->downsample >= 1.f)) return MGS_ERR_BAD_ARGUMENT;   // NaN fails too
+  const double most = floor((double)a->width * (double)a->height / (double)a->downsample);
+  if ((double)a->row_capacity < most) return MGS_ERR_BAD_ARGUMENT;
+  if (!a->image || !a->T || !a->exposure_a || !a->exposure_b || !a->xyz || !a->features_dc || !a->log_scales ||
+      !a->rots || !a->opacity_logit || !a->scratch || !a->result || !a->result_host)
+    return MGS_ERR_BAD_ARGUMENT;
+  if ((a->mode != 1 && !a->depth) || (a->mode == 0 && !a->opacity)) return MGS_ERR_BAD_ARGUMENT;
+  if (reinterpret_cast<uintptr_t>(a->scratch) & 15u) return MGS_ERR_BAD_ARGUMENT;
+  return MGS_OK;
+}
+
+extern "C" {
+
+uint64_t mgs_keyframe_seed_scratch_bytes(int32_t num_pixels, int32_t row_capacity) {
+  if (num_pixels < 1 || row_capacity < 1) return 0;
+  return keyframe_seed_scratch_bytes(num_pixels, row_capacity);
+}
+
+int32_t mgs_keyframe_seed(const mgs_keyframe_seed_args* args, void* stream) {
+  const int32_t rc = keyframe_seed_args_status(args);
+  if (rc != MGS_OK) return rc;
+  return launch_keyframe_seed(*args, (hipStream_t)stream);
 }
 
 }  // extern "C"

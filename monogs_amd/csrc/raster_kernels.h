@@ -254,6 +254,14 @@ struct KfLayout { uint64_t hist1, hist2, hist3, ticket, partials, bytes; int bp,
 KfLayout kf_layout(int num_gaussians, int num_pixels);
 int launch_keyframe_decide(const mgs_keyframe_args& A, hipStream_t st);
 
+// simple-knn (knn.hip, mgs_knn_dist2; mgs_keyframe_seed runs the same launcher for its scales).
+int launch_knn(const float* pts, int n, float* out, void* scratch, hipStream_t st);
+uint64_t knn_scratch_bytes(int n);
+
+// Keyframe seeding (keyframe_seed.hip, mgs_keyframe_seed).
+uint64_t keyframe_seed_scratch_bytes(int num_pixels, int row_capacity);
+int launch_keyframe_seed(const mgs_keyframe_seed_args& A, hipStream_t st);
+
 inline Layout make_layout(const mgs_raster_shape& s) {
   Layout L;
   const uint64_t N = (uint64_t)s.num_gaussians;

@@ -226,6 +226,13 @@ class GaussianModel:
         pcd = self.create_pcd_from_image(cam_info, init, scale=scale, depthmap=depthmap, generator=generator)
         self.extend_from_pcd(*pcd, kf_id)
 
+    def extend_from_keyframe(self, seeder, cam, image, depth, opacity, mode, init, seed, kf_id, noise=None, keys=None):
+        """Keyframe insertion through the native seeding path (keyframe_seed.KeyframeSeeder: depth prior, sub-sample,
+        back-projection and k-nn scale in one mgs_keyframe_seed call), then the append.  Returns the seeder's record."""
+        xyz, feats, scales, rots, opac, rec = seeder.seed(cam, image, depth, opacity, mode, init, seed, noise, keys)
+        self.extend_from_pcd(xyz, feats, scales, rots, opac, kf_id)
+        return rec
+
     # ---- maintenance (:364-377, :485-697) ---------------------------------------------------------
     def _reset(self, mode: int, value: float, denom_inc: Optional[torch.Tensor]):
         n = len(self)

@@ -140,7 +140,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  init_iters: int = 1050, mapping_iters: int = 150, first_order_iters: int = 40,
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
-                 alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None):
+                 alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
+                 native_keyframe_seed: bool = False):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -151,7 +152,10 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     (keyframe_policy.py; its window_size and kf_interval are used), and a monocular reset re-initialises a fresh map
     on the frame that triggered it, at its ground-truth pose - the reference's loop reads that frame again
     (:1942-1950, initialize :236-252).  The result then also holds `decisions` (one per tracked frame), `windows`
-    (the window after each tracked frame) and `resets` (the frames that re-initialised the map)."""
+    (the window after each tracked frame) and `resets` (the frames that re-initialised the map).
+    `native_keyframe_seed`: the three insertion sites (first frame, reset, keyframe) go through
+    keyframe_seed.KeyframeSeeder (one mgs_keyframe_seed call and one host read each) instead of keyframe_depth +
+    extend_from_pcd_seq; the result then also holds `seed_records` ({frame: the call's record})."""
     if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
         raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
     policy = keyframe_policy
@@ -171,6 +175,23 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     gm.init_lr(6.0)
     gm.training_setup()
     mapper = NativeMapper(gm, bg, config=cfg, cameras_extent=6.0, seed=seed)
+    seeder, seed_records = None, {}
+    if native_keyframe_seed:
+        from .keyframe_seed import MODE_INITIAL, MODE_RENDERED, MODE_SENSOR, KeyframeSeeder
+        seeder = KeyframeSeeder(H, W, dev, cfg, isotropic=gm.isotropic, max_sh_degree=gm.max_sh_degree)
+
+    def insert(gm_, fr: Frame, view, k, init, depth=None, opacity=None):
+        """New Gaussians of keyframe k: add_new_keyframe's depth map, then create_pcd + extend_from_pcd."""
+        if seeder is None:
+            dm = keyframe_depth(fr.image, depth, opacity, fr.depth if sensor_depth else None, gen)
+            gm_.extend_from_pcd_seq(view, kf_id=k, init=init, depthmap=dm, generator=gen)
+            return
+        if sensor_depth:
+            mode, depth, opacity = MODE_SENSOR, fr.depth, None
+        else:
+            mode = MODE_INITIAL if depth is None else MODE_RENDERED
+        seed_records[k] = gm_.extend_from_keyframe(seeder, view, fr.image, depth, opacity, mode, init,
+                                                   seed * 1_000_003 + k, kf_id=k)
 
     def camera(fr: Frame, T):
         v = ViewCamera(fr.uid, fr.image, T, cam.projmatrix_raw, fovx, fovy, H, W, dev,
@@ -186,8 +207,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     cams[0] = camera(f0, f0.T_gt.to(dev).float().clone())
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    d0 = keyframe_depth(f0.image, None, None, f0.depth if sensor_depth else None, gen)
-    gm.extend_from_pcd_seq(cams[0], kf_id=0, init=True, depthmap=d0, generator=gen)
+    insert(gm, f0, cams[0], 0, True)
     mapper.add_keyframe(0, cams[0])
     mapper.set_window([0])
     mapper.initialize_map(0, iters=init_iters)
@@ -233,8 +253,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                 gm.training_setup()
                 mapper = NativeMapper(gm, bg, config=cfg, cameras_extent=6.0, seed=seed)
                 cams[k] = camera(fr, fr.T_gt.to(dev).float().clone())
-                dk = keyframe_depth(fr.image, None, None, fr.depth if sensor_depth else None, gen)
-                gm.extend_from_pcd_seq(cams[k], kf_id=k, init=True, depthmap=dk, generator=gen)
+                insert(gm, fr, cams[k], k, True)
                 mapper.add_keyframe(k, cams[k])
                 mapper.set_window([k])
                 mapper.initialize_map(k, iters=init_iters)
@@ -246,8 +265,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         if create_kf:
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-            depth_map = keyframe_depth(fr.image, trk.depth, trk.opacity, fr.depth if sensor_depth else None, gen)
-            gm.extend_from_pcd_seq(vp, kf_id=k, init=False, depthmap=depth_map, generator=gen)
+            insert(gm, fr, vp, k, False, trk.depth, trk.opacity)
             window = new_window
             kf_ids.append(k)
             last_kf = k
@@ -266,10 +284,13 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                 log(f"keyframe {k}: window {window}, {len(gm)} Gaussians, loss {float(mapper.last_loss):.4f}")
         windows.append(list(window))
     ok = mapper.check_capacity()
-    return {"cameras": cams, "kf_ids": kf_ids, "gaussians": gm, "mapper": mapper, "t_init": t_init,
-            "t_track": t_track, "t_map": t_map, "n_track_iters": n_track_iters, "n_map_iters": n_map_iters,
-            "n_map_views": n_map_views, "capacity_ok": ok, "frames_tracked": len(frames) - 1,
-            "decisions": decisions, "windows": windows, "resets": resets}
+    result = {"cameras": cams, "kf_ids": kf_ids, "gaussians": gm, "mapper": mapper, "t_init": t_init,
+              "t_track": t_track, "t_map": t_map, "n_track_iters": n_track_iters, "n_map_iters": n_map_iters,
+              "n_map_views": n_map_views, "capacity_ok": ok, "frames_tracked": len(frames) - 1,
+              "decisions": decisions, "windows": windows, "resets": resets}
+    if seeder is not None:
+        result["seed_records"] = seed_records
+    return result
 
 
 def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
