@@ -10,6 +10,7 @@ import numpy as np
 import torch
 
 from conftest import gpu_settings, oracle_settings, rel_err
+from map_models import _make_model, _state_of
 
 pytestmark = pytest.mark.gpu
 
@@ -1114,41 +1115,6 @@ def test_keyframe_insertion_on_device(built):
 # ---------------------------------------------------------------------------------------
 # map maintenance on the device
 # ---------------------------------------------------------------------------------------
-class _Model:
-    """GaussianModel-shaped holder (gaussian_model.py:30-52, :247-285)."""
-    percent_dense = 0.01
-
-
-def _make_model(n, dev, seed, fused, rest=0):
-    from monogs_amd.map_update import FusedGaussianAdam
-    g = torch.Generator().manual_seed(seed)
-    cpu = {
-        "xyz": torch.randn(n, 3, generator=g),
-        "f_dc": torch.randn(n, 1, 3, generator=g),
-        "f_rest": torch.randn(n, rest, 3, generator=g),
-        "opacity": torch.randn(n, 1, generator=g) * 2.0,
-        "scaling": torch.randn(n, 3, generator=g) * 0.7 - 3.0,
-        "rotation": torch.randn(n, 4, generator=g),
-    }
-    m = _Model()
-    import torch.nn as nn
-    attr = {"xyz": "_xyz", "f_dc": "_features_dc", "f_rest": "_features_rest", "opacity": "_opacity",
-            "scaling": "_scaling", "rotation": "_rotation"}
-    groups = []
-    lrs = {"xyz": 1.6e-4, "f_dc": 2.5e-3, "f_rest": 1.25e-4, "opacity": 0.05, "scaling": 1e-3, "rotation": 1e-3}
-    for name, t in cpu.items():
-        p = nn.Parameter(t.clone().to(dev))
-        setattr(m, attr[name], p)
-        groups.append({"params": [p], "lr": lrs[name], "name": name})
-    m.optimizer = FusedGaussianAdam(groups, lr=0.0, eps=1e-15) if fused else torch.optim.Adam(groups, lr=0.0, eps=1e-15)
-    m.xyz_gradient_accum = (torch.rand(n, 1, generator=g) * 4e-4).to(dev)
-    m.denom = torch.randint(0, 3, (n, 1), generator=g).float().to(dev)      # zeros -> NaN grads
-    m.max_radii2D = torch.rand(n, generator=g).to(dev) * 30
-    m.unique_kfIDs = torch.randint(0, 9, (n,), generator=g).int().to(dev)
-    m.n_obs = torch.randint(0, 5, (n,), generator=g).int().to(dev)
-    return m, cpu, attr
-
-
 def test_fused_gaussian_adam_matches_torch_adam(built):
     dev = _dev()
     ma, cpu, attr = _make_model(3001, dev, 7, fused=True, rest=3)
@@ -1173,20 +1139,6 @@ def test_fused_gaussian_adam_matches_torch_adam(built):
         sa, sb = ma.optimizer.state[pa], mb.optimizer.state[pb]
         assert torch.allclose(sa["exp_avg"], sb["exp_avg"], rtol=1e-5, atol=1e-7), name   # lerp rounding
         assert torch.allclose(sa["exp_avg_sq"], sb["exp_avg_sq"], rtol=1e-5, atol=1e-10), name
-
-
-def _state_of(m, attr, cpu_names):
-    st = {}
-    for name, a in attr.items():
-        p = getattr(m, a)
-        st[name] = p.detach().cpu().clone()
-        s = m.optimizer.state.get(p)
-        st["exp_avg_" + name] = s["exp_avg"].cpu().clone()
-        st["exp_avg_sq_" + name] = s["exp_avg_sq"].cpu().clone()
-    st["kf"], st["n_obs"] = m.unique_kfIDs.cpu().clone(), m.n_obs.cpu().clone()
-    st["grad_accum"], st["denom"] = m.xyz_gradient_accum.cpu().clone(), m.denom.cpu().clone()
-    st["max_radii"] = m.max_radii2D.cpu().clone()
-    return st
 
 
 @pytest.mark.parametrize("fused,max_screen_size,rest", [(True, 20, 0), (False, None, 3)])
