@@ -778,6 +778,68 @@ uint64_t mgs_keyframe_seed_scratch_bytes(int32_t num_pixels, int32_t row_capacit
  * MGS_ERR_BAD_ARGUMENT.  Synchronises `stream` once. */
 int32_t mgs_keyframe_seed(const mgs_keyframe_seed_args* args, void* stream);
 
+/* ---- frame preparation on the device (frame_prepare.hip) ---------------------------------
+ * What the reference does to EVERY incoming frame before tracking: the dataset's conversion (utils/dataset.py:269-276)
+ * and Camera.compute_grad_mask (utils/camera_utils.py:110-147, stencils utils/slam_utils.py:7-41), stream-ordered, with
+ * no host read and no synchronisation.
+ *   ingest     uint8 [H][W][3] image: value = (float)(k / 255.0) (a double quotient rounded once, NumPy's);
+ *              uint16 [H][W] depth: value = (float)(d / depth_scale), likewise a double quotient.
+ *   sum, grey  s = (r + g) + b (two roundings, in this order); grey = s / 3.
+ *   masks      rgb_pixel_mask_mapping = s > rgb_boundary_threshold;  rgb_pixel_mask = rgb_pixel_mask_mapping * grad_mask.
+ *   gradient   3x3 cross-correlation (not flipped) over the reflect-padded grey (index -1 -> 1, H -> H - 2), times
+ *              1 / 32: grad_v with [[3,10,3],[0,0,0],[-3,-10,-3]], grad_h with [[3,0,-3],[10,0,-10],[3,0,-3]].
+ *              A pixel is valid when all nine padded neighbours have |grey| > 0.01; otherwise both gradients are 0.
+ *              intensity I = sqrt(grad_v^2 + grad_h^2).
+ *   global     m = the lower median of all H*W intensities (rank (H*W - 1) / 2, torch.median's element; a three-level
+ *              radix select, no sort); grad_mask = I > m * edge_threshold (the product rounded to fp32).
+ *   patch      (the reference's Replica branch) 32x32 patches, stride 32, anchored top-left, floor(H/32) x floor(W/32)
+ *              of them; m_p = the element of rank 511 of a patch's 1024 intensities; grad_mask = I > m_p *
+ *              edge_threshold inside the patches and 0 on every pixel that no whole patch covers.
+ * Histogram counting is integer: two calls with the same inputs give bit-identical outputs.  NaN / Inf in the image:
+ * unspecified (no out-of-bounds access; the masks and medians are then whatever the comparisons give). */
+#define MGS_FRAME_IMAGE_F32_CHW 0
+#define MGS_FRAME_IMAGE_U8_HWC 1
+#define MGS_FRAME_DEPTH_NONE 0
+#define MGS_FRAME_DEPTH_F32 1
+#define MGS_FRAME_DEPTH_U16 2
+#define MGS_FRAME_MODE_GLOBAL 0
+#define MGS_FRAME_MODE_PATCH 1
+#define MGS_FRAME_PATCH_SIZE 32
+
+typedef struct mgs_frame_prepare_args {
+  int32_t width, height;           /* both >= 2 (reflect padding); patch mode: both >= 32 */
+  int32_t mode;                    /* MGS_FRAME_MODE_* */
+  int32_t image_format;            /* MGS_FRAME_IMAGE_* */
+  int32_t depth_format;            /* MGS_FRAME_DEPTH_* */
+  float edge_threshold;
+  float rgb_boundary_threshold;
+  int32_t reserved0;
+  double depth_scale;              /* uint16 depth only; > 0 */
+  const void* image_in;            /* float [3][H][W] or uint8 [H][W][3] */
+  const void* depth_in;            /* float [H][W] or uint16 [H][W]; NULL without depth */
+  float* image;                    /* [3][H][W] the float image; required for uint8 input, for float input optional
+                                      (a copy; NULL or image_in itself: nothing is written) */
+  float* gt_depth;                 /* [1][H][W]; required for uint16 input, for float input optional likewise */
+  float* grad_mask;                /* [1][H][W] 0 / 1 */
+  float* rgb_pixel_mask;           /* [1][H][W] 0 / 1 */
+  float* rgb_pixel_mask_mapping;   /* [1][H][W] 0 / 1 */
+  float* median_out;               /* device; global: 1 float, patch: floor(H/32) * floor(W/32), row-major; or NULL */
+  float* intensity_out;            /* [H][W] the gradient intensity, or NULL */
+  void* scratch;                   /* mgs_frame_prepare_scratch_bytes(H, W) bytes, 16-byte aligned; the call zeroes
+                                      what it counts in itself: no memset is asked of the caller */
+} mgs_frame_prepare_args;
+
+/* sizeof(mgs_frame_prepare_args), for a binding to verify its mirror.  The list behind mgs_struct_size() ends at index
+ * 25 (bindings and tests rely on -1 from 26 on), so this struct answers for itself. */
+int32_t mgs_frame_prepare_args_size(void);
+/* 0 for sizes the call refuses. */
+uint64_t mgs_frame_prepare_scratch_bytes(int32_t H, int32_t W);
+/* Every argument is checked before anything is launched or written: a null required pointer, H or W < 2 (< 32 in patch
+ * mode), an unknown mode / format, depth_scale <= 0 (or NaN) with uint16 depth, a scratch address that is not 16-byte
+ * aligned give MGS_ERR_BAD_ARGUMENT; an image beyond 2^31 - 1 pixels or 65 535 tiles a side MGS_ERR_UNSUPPORTED.
+ * Global mode: one memset node and four launches; patch mode: one launch.  No host read, no synchronisation. */
+int32_t mgs_frame_prepare(const mgs_frame_prepare_args* args, void* stream);
+
 /* ---- map maintenance on the device ---------------------------------- */
 
 #define MGS_ADAM_MAX_GROUPS 8

@@ -30,6 +30,7 @@ EXPORTS = (
     "mgs_tracking_iteration_rgbd", "mgs_tracking_iteration_second_order_rgbd", "mgs_tracking_loss_rgbd_fused",
     "mgs_sketch_residual_rgbd", "mgs_tracking_sample_scratch_bytes", "mgs_tracking_iteration_sampled",
     "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide", "mgs_keyframe_seed_scratch_bytes", "mgs_keyframe_seed",
+    "mgs_frame_prepare_args_size", "mgs_frame_prepare_scratch_bytes", "mgs_frame_prepare",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -253,6 +254,20 @@ class KeyframeSeedArgs(C.Structure):
                 + [("result_host", C.POINTER(KeyframeSeedResult))])
 
 
+FRAME_IMAGE_F32_CHW, FRAME_IMAGE_U8_HWC = 0, 1
+FRAME_DEPTH_NONE, FRAME_DEPTH_F32, FRAME_DEPTH_U16 = 0, 1, 2
+FRAME_MODE_GLOBAL, FRAME_MODE_PATCH = 0, 1
+FRAME_PATCH_SIZE = 32
+
+
+class FramePrepareArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "mode", "image_format", "depth_format")]
+                + [("edge_threshold", C.c_float), ("rgb_boundary_threshold", C.c_float), ("reserved0", C.c_int32),
+                   ("depth_scale", C.c_double)]
+                + [(n, _fp) for n in ("image_in", "depth_in", "image", "gt_depth", "grad_mask", "rgb_pixel_mask",
+                                      "rgb_pixel_mask_mapping", "median_out", "intensity_out", "scratch")])
+
+
 _lib = None
 
 
@@ -380,6 +395,14 @@ def lib():
     L.mgs_keyframe_seed_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     L.mgs_keyframe_seed.restype = C.c_int32
     L.mgs_keyframe_seed.argtypes = [C.POINTER(KeyframeSeedArgs), C.c_void_p]
+    L.mgs_frame_prepare_args_size.restype = C.c_int32
+    L.mgs_frame_prepare_args_size.argtypes = []
+    if L.mgs_frame_prepare_args_size() != C.sizeof(FramePrepareArgs):     # not in mgs_struct_size()'s list: checked here
+        raise NativeLibraryError("FramePrepareArgs does not have the size of mgs_frame_prepare_args")
+    L.mgs_frame_prepare_scratch_bytes.restype = C.c_uint64
+    L.mgs_frame_prepare_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.mgs_frame_prepare.restype = C.c_int32
+    L.mgs_frame_prepare.argtypes = [C.POINTER(FramePrepareArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

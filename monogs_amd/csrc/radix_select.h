@@ -60,6 +60,60 @@ __device__ void block_select(const int* hist, int k, int* s_scan, int* s_out) {
   block_select_by<THREADS, PER>(hist, [k](int total) { return k < 0 ? (total - 1) / 2 : k; }, s_scan, s_out);
 }
 
+// ---- the pieces of a three-level select over global histograms, for kernels of THREADS threads (frame_prepare.hip;
+// keyframe_seed.hip keeps its own, older copies) ---------------------------------------------------------------------
+struct RadixHists { int *h1, *h2, *h3; };
+
+// The first `levels` levels of the select of the lower median, repeated by every workgroup.  prefix = the selected
+// key's top bits (11, 22 or all 32), rank = the rank left inside that bucket, total = the histogram's own total;
+// any = false when the histogram is empty.  s_scan holds THREADS / 64 ints, s_sel 3.  All threads call it.
+struct RadixSelected { unsigned prefix; int rank, total; bool any; };
+template <int THREADS>
+__device__ RadixSelected radix_select_median(const RadixHists& H, int levels, int* s_scan, int* s_sel) {
+  RadixSelected r;
+  block_select<THREADS, kRadixHist1 / THREADS>(H.h1, -1, s_scan, s_sel);
+  r.total = s_sel[2];
+  r.any = s_sel[0] >= 0;
+  r.prefix = (unsigned)s_sel[0];
+  r.rank = s_sel[1];
+  if (levels >= 2 && r.any) {
+    const int k2 = r.rank;
+    __syncthreads();
+    block_select<THREADS, kRadixHist2 / THREADS>(H.h2, k2, s_scan, s_sel);
+    r.prefix = r.prefix << 11 | (unsigned)s_sel[0];
+    r.rank = s_sel[1];
+    if (levels >= 3) {
+      const int k3 = r.rank;
+      __syncthreads();
+      block_select<THREADS, kRadixHist3 / THREADS>(H.h3, k3, s_scan, s_sel);
+      r.prefix = r.prefix << 10 | (unsigned)s_sel[0];
+      r.rank = s_sel[1];
+    }
+  }
+  __syncthreads();
+  return r;
+}
+
+// One LDS increment per distinct bucket and wave: image statistics share a few top-bit buckets.  All lanes call it.
+__device__ __forceinline__ void radix_hist_add_aggregated(int* s_hist, bool ok, unsigned b) {
+  unsigned long long pending = __ballot(ok);
+  while (pending) {
+    const unsigned lb = (unsigned)__shfl((int)b, __ffsll((long long)pending) - 1);
+    const unsigned long long same = __ballot(ok && b == lb) & pending;
+    if (ok && b == lb && __ffsll((long long)same) - 1 == (int)(threadIdx.x & 63)) atomicAdd(&s_hist[lb], __popcll(same));
+    pending &= ~same;
+  }
+}
+
+// The workgroup's LDS histogram into the global one: integer atomics, so the sum does not depend on arrival order.
+template <int THREADS>
+__device__ __forceinline__ void radix_hist_flush(const int* s_hist, int* out, int nb) {
+  for (int b = threadIdx.x; b < nb; b += THREADS) {
+    const int v = s_hist[b];
+    if (v) atomicAdd(&out[b], v);
+  }
+}
+
 // uint32 keys in the order of the floats they came from (negative values below positive ones; -0 below +0).
 __device__ __forceinline__ unsigned float_order_key(float x) {
   const unsigned b = __float_as_uint(x);

@@ -141,7 +141,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
-                 native_keyframe_seed: bool = False):
+                 native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -155,7 +155,15 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     (the window after each tracked frame) and `resets` (the frames that re-initialised the map).
     `native_keyframe_seed`: the three insertion sites (first frame, reset, keyframe) go through
     keyframe_seed.KeyframeSeeder (one mgs_keyframe_seed call and one host read each) instead of keyframe_depth +
-    extend_from_pcd_seq; the result then also holds `seed_records` ({frame: the call's record})."""
+    extend_from_pcd_seq; the result then also holds `seed_records` ({frame: the call's record}).
+    `native_frame_prepare`: every frame goes through one frame_prepare.FramePreparer (one mgs_frame_prepare call, the
+    reference's per-frame compute_grad_mask) when its camera is made, inside the timed tracking section (frame 0:
+    initialisation): the camera's grad_mask, rgb_pixel_mask, rgb_pixel_mask_mapping (and gt_depth with `sensor_depth`)
+    are the preparer's, with Training.edge_threshold / rgb_boundary_threshold and Dataset.type from `config`; the
+    result then also holds `t_prepare`, the host time spent enqueuing those calls.  `track_on_edges` (needs
+    native_frame_prepare): tracking takes rgb_pixel_mask, upstream MonoGS's high-gradient pixels, as its pixel mask."""
+    if track_on_edges and not native_frame_prepare:
+        raise ValueError("track_on_edges needs native_frame_prepare=True (the edge mask is the preparer's)")
     if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
         raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
     policy = keyframe_policy
@@ -179,6 +187,10 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     if native_keyframe_seed:
         from .keyframe_seed import MODE_INITIAL, MODE_RENDERED, MODE_SENSOR, KeyframeSeeder
         seeder = KeyframeSeeder(H, W, dev, cfg, isotropic=gm.isotropic, max_sh_degree=gm.max_sh_degree)
+    preparer, t_prepare = None, 0.0
+    if native_frame_prepare:
+        from .frame_prepare import FramePreparer
+        preparer = FramePreparer(H, W, dev, cfg)
 
     def insert(gm_, fr: Frame, view, k, init, depth=None, opacity=None):
         """New Gaussians of keyframe k: add_new_keyframe's depth map, then create_pcd + extend_from_pcd."""
@@ -197,6 +209,11 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         v = ViewCamera(fr.uid, fr.image, T, cam.projmatrix_raw, fovx, fovy, H, W, dev,
                        intrinsics=(cam.fx, cam.fy, cam.cx, cam.cy))
         v.T_gt = fr.T_gt
+        if preparer is not None:
+            nonlocal t_prepare
+            tp = time.perf_counter()
+            preparer.prepare_into(v, fr.image, fr.depth if sensor_depth else None)
+            t_prepare += time.perf_counter() - tp
         return v
 
     t_track = t_map = 0.0
@@ -219,11 +236,15 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     decisions, windows, resets = [], [], []
     for k in range(1, len(frames)):
         fr = frames[k]
-        vp = camera(fr, cams[k - 1].T.detach().clone())           # previous pose (:358-362)
+        if preparer is None:
+            vp = camera(fr, cams[k - 1].T.detach().clone())       # previous pose (:358-362)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
+        if preparer is not None:                                  # the frame's preparation is part of its tracking time
+            vp = camera(fr, cams[k - 1].T.detach().clone())
         trk = NativeTracker(vp, gm, bg, gt_depth=fr.depth if rgbd_tracking else None, alpha=alpha,
-                            num_pixels=num_pixels, sample_seed=seed + k)
+                            num_pixels=num_pixels, sample_seed=seed + k,
+                            mask=vp.rgb_pixel_mask if track_on_edges else None)
         if second_order_iters > 0:
             trk.enable_second_order(stack_dim=16, sketch_dim=64, initial_lambda=1e-3, seed=seed + k)
         # one frame of the reference's loop incl. its best-iterate bookkeeping (slam_frontend.py:455-822;
@@ -290,6 +311,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
               "decisions": decisions, "windows": windows, "resets": resets}
     if seeder is not None:
         result["seed_records"] = seed_records
+    if preparer is not None:
+        result["t_prepare"] = t_prepare
     return result
 
 

@@ -33,7 +33,7 @@ class NativeTracker:
     def __init__(self, viewpoint, gaussians, background, huber_delta=0.01, lr_rot=0.003,
                  lr_trans=0.001, lr_a=0.02, lr_b=0.02, betas=(0.9, 0.999), eps=1e-8,
                  converged_threshold=1e-4, capacity_margin=1.5, pnorm=2.0, gt_depth=None, alpha=0.95, num_pixels=-1,
-                 sample_seed=0):
+                 sample_seed=0, mask=None):
         # (huber_delta, pnorm) as slam_loops.tracking_norm(config) returns them: the reference's first-order
         # objective is Huber + L2 when RGN.use_huber, else the RGN.pnorm-norm without Huber (huber_delta = 0),
         # slam_frontend.py:596-600.  p = 1 and p = 2 ride in the forward blend's epilogue, any other p >= 1
@@ -44,6 +44,9 @@ class NativeTracker:
         # num_pixels = K > 0 (RGN.first_order.num_pixels, slam_loops.sampled_num_pixels): every first-order step() takes
         # the pixel-sampled gradient of K pixels (mgs_tracking_iteration_sampled; DESIGN.md "Pixel-sampled first-order
         # tracking"), drawn on the device with the key (sample_seed, sampled iteration); <= 0 keeps the dense step.
+        # mask ([H,W] or [1,H,W], 0 / 1): the pixel mask of the objective, in place of the viewpoint's
+        # rgb_pixel_mask_mapping attribute.  Upstream MonoGS tracks on high-gradient pixels (get_loss_tracking_rgb,
+        # utils/slam_utils.py:91-100): pass frame_prepare's rgb_pixel_mask.
         vp = viewpoint
         dev = vp.T.device
         if dev.type != "cuda":
@@ -66,7 +69,9 @@ class NativeTracker:
         self.full = torch.empty(4, 4, device=dev)
         self.bg = f32(background).reshape(-1)
         self.gt = f32(vp.original_image)
-        m = getattr(vp, "rgb_pixel_mask_mapping", None)
+        m = mask if mask is not None else getattr(vp, "rgb_pixel_mask_mapping", None)
+        if mask is not None and m.numel() != int(vp.image_height) * int(vp.image_width):
+            raise ValueError(f"mask has {m.numel()} elements, the image {int(vp.image_height) * int(vp.image_width)}")
         self.mask = None if m is None else f32(m)
         lib = _cabi.lib()
         stream = self._stream()
