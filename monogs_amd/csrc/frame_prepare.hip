@@ -22,6 +22,8 @@
 #include "../../include/monogs_raster.h"
 #include "launch.h"
 #include "radix_select.h"
+#include "raster_kernels.h"
+#include "rn_math.h"
 
 namespace mgs {
 
@@ -43,26 +45,14 @@ struct FpScratch {
 
 struct FpLayout { uint64_t hists, zero_bytes, intensity, bytes; };
 
-constexpr uint64_t fp_align(uint64_t x) { return (x + 255u) & ~uint64_t(255); }
-
 FpLayout fp_layout(uint64_t num_pixels) {
   FpLayout L;
   uint64_t o = 0;
-  L.hists = o; o = fp_align(o + (uint64_t)(kRadixHist1 + kRadixHist2 + kRadixHist3) * 4);
+  L.hists = o; o = align_up(o + (uint64_t)kRadixHistInts * 4);
   L.zero_bytes = o;
-  L.intensity = o; o = fp_align(o + num_pixels * 4);
+  L.intensity = o; o = align_up(o + num_pixels * 4);
   L.bytes = o;
   return L;
-}
-
-// Single roundings the torch mirror reproduces: the pragma keeps the default contraction from fusing them into an fma.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
 }
 
 // torch's "reflect" padding of one pixel (-1 -> 1, n -> n - 2), then clamped: a tile's halo may hang over the image by
@@ -166,7 +156,8 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_intensity(const mgs_frame_pre
       S.intensity[p] = I;
       A.rgb_pixel_mask_mapping[p] = s_sum[(ty + 1) * P + tx + 1] > A.rgb_boundary_threshold ? 1.f : 0.f;
     }
-    radix_hist_add_aggregated(s_hist, in, __float_as_uint(I) >> 21);   // I >= 0: the bit pattern orders like the value
+    // I >= 0: the bit pattern orders like the value
+    radix_hist_add_aggregated(s_hist, in, radix_level<1>(__float_as_uint(I), 0u).bucket);
   }
   __syncthreads();
   radix_hist_flush<kFpThreads>(s_hist, S.hist.h1, kRadixHist1);
@@ -178,28 +169,28 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_level(const FpScratch S, int 
   __shared__ int s_scan[kFpWaves];
   __shared__ int s_sel[3];
   const int tid = threadIdx.x;
-  constexpr int nb = PASS == 3 ? kRadixHist3 : kRadixHist2;
+  constexpr int nb = radix_level_buckets(PASS);
   for (int b = tid; b < nb; b += kFpThreads) s_hist[b] = 0;
-  const RadixSelected sel = radix_select_median<kFpThreads>(S.hist, PASS - 1, s_scan, s_sel);   // ends in a barrier
+  // ends in a barrier: the histogram is clear before any wave adds to it
+  const RadixSelected sel = radix_select<kFpThreads>(S.hist, PASS - 1, LowerMedianRank{}, s_scan, s_sel);
   for (int base = blockIdx.x * kFpStep; base < HW; base += gridDim.x * kFpStep) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int i = base + j * kFpThreads + tid;
       if (i >= HW) continue;
-      const unsigned bits = __float_as_uint(S.intensity[i]);
-      if (PASS == 2 && (bits >> 21) == sel.prefix) atomicAdd(&s_hist[(bits >> 10) & 2047u], 1);
-      if (PASS == 3 && (bits >> 10) == sel.prefix) atomicAdd(&s_hist[bits & 1023u], 1);
+      const RadixBucket rb = radix_level<PASS>(__float_as_uint(S.intensity[i]), sel.prefix);
+      if (rb.counts) atomicAdd(&s_hist[rb.bucket], 1);
     }
   }
   __syncthreads();
-  radix_hist_flush<kFpThreads>(s_hist, PASS == 2 ? S.hist.h2 : S.hist.h3, nb);
+  radix_hist_flush<kFpThreads>(s_hist, S.hist.level(PASS), nb);
 }
 
 __global__ __launch_bounds__(kFpThreads) void k_fp_threshold(const mgs_frame_prepare_args A, const FpScratch S, int HW) {
   __shared__ int s_scan[kFpWaves];
   __shared__ int s_sel[3];
   const int tid = threadIdx.x;
-  const RadixSelected sel = radix_select_median<kFpThreads>(S.hist, 3, s_scan, s_sel);
+  const RadixSelected sel = radix_select<kFpThreads>(S.hist, 3, LowerMedianRank{}, s_scan, s_sel);
   const float m = __uint_as_float(sel.prefix);
   const float thr = mul_rn(m, A.edge_threshold);
   if (blockIdx.x == 0 && tid == 0 && A.median_out) A.median_out[0] = m;
@@ -216,6 +207,26 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_threshold(const mgs_frame_pre
 }
 
 // ---- patch mode -------------------------------------------------------------------------------------------------------
+// One level of the in-LDS select of a patch's PER * kFpThreads intensities: histogram, then the whole workgroup searches
+// it.  prefix and rank carry the selection from level to level.  All threads call it.
+template <int LEVEL, int PER>
+__device__ __forceinline__ void patch_select_level(const float (&I)[PER], int* s_hist, int* s_scan, int* s_sel,
+                                                   unsigned& prefix, int& rank) {
+  constexpr int nb = radix_level_buckets(LEVEL);
+  for (int b = threadIdx.x; b < nb; b += kFpThreads) s_hist[b] = 0;
+  __syncthreads();
+#pragma unroll
+  for (int j = 0; j < PER; j++) {
+    const RadixBucket rb = radix_level<LEVEL>(__float_as_uint(I[j]), prefix);
+    if (rb.counts) atomicAdd(&s_hist[rb.bucket], 1);
+  }
+  __syncthreads();
+  block_select<kFpThreads, nb / kFpThreads>(s_hist, rank, s_scan, s_sel);
+  prefix = prefix << (LEVEL == 3 ? 10 : 11) | (unsigned)s_sel[0];
+  rank = s_sel[1];
+  __syncthreads();   // s_sel is read before the next level's search writes it
+}
+
 __global__ __launch_bounds__(kFpThreads) void k_fp_patch(const mgs_frame_prepare_args A) {
   constexpr int P = kFpPatch + 2, PER = kFpPatch * kFpPatch / kFpThreads;
   __shared__ float s_lut[256];
@@ -252,28 +263,9 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_patch(const mgs_frame_prepare
   // rank 511 of the 1024 intensities: three histogram levels in LDS, each searched by the whole workgroup
   unsigned prefix = 0u;
   int rank = kFpPatchRank;
-#pragma unroll
-  for (int level = 1; level <= 3; level++) {
-    for (int b = tid; b < kRadixHist1; b += kFpThreads) s_hist[b] = 0;
-    __syncthreads();
-#pragma unroll
-    for (int j = 0; j < PER; j++) {
-      const unsigned bits = __float_as_uint(I[j]);
-      if (level == 1) atomicAdd(&s_hist[bits >> 21], 1);
-      if (level == 2 && (bits >> 21) == prefix) atomicAdd(&s_hist[(bits >> 10) & 2047u], 1);
-      if (level == 3 && (bits >> 10) == prefix) atomicAdd(&s_hist[bits & 1023u], 1);
-    }
-    __syncthreads();
-    if (level < 3) {
-      block_select<kFpThreads, kRadixHist1 / kFpThreads>(s_hist, rank, s_scan, s_sel);
-      prefix = prefix << 11 | (unsigned)s_sel[0];
-    } else {
-      block_select<kFpThreads, kRadixHist3 / kFpThreads>(s_hist, rank, s_scan, s_sel);
-      prefix = prefix << 10 | (unsigned)s_sel[0];
-    }
-    rank = s_sel[1];
-    __syncthreads();   // s_sel is read before the next level's search writes it
-  }
+  patch_select_level<1>(I, s_hist, s_scan, s_sel, prefix, rank);
+  patch_select_level<2>(I, s_hist, s_scan, s_sel, prefix, rank);
+  patch_select_level<3>(I, s_hist, s_scan, s_sel, prefix, rank);
   const float m = __uint_as_float(prefix);
   const float thr = mul_rn(m, A.edge_threshold);
   if (tid == 0 && A.median_out) A.median_out[blockIdx.y * (W / kFpPatch) + blockIdx.x] = m;
@@ -315,9 +307,7 @@ int launch_frame_prepare(const mgs_frame_prepare_args& A, hipStream_t st) {
   const FpLayout L = fp_layout((uint64_t)HW);
   char* w = static_cast<char*>(A.scratch);
   FpScratch S{};
-  S.hist.h1 = reinterpret_cast<int*>(w + L.hists);
-  S.hist.h2 = S.hist.h1 + kRadixHist1;
-  S.hist.h3 = S.hist.h2 + kRadixHist2;
+  S.hist = radix_hists_at(w + L.hists);
   S.intensity = A.intensity_out ? A.intensity_out : reinterpret_cast<float*>(w + L.intensity);
   int hb = (HW + kFpStep - 1) / kFpStep;
   hb = hb > kFpMaxBlocks ? kFpMaxBlocks : hb;

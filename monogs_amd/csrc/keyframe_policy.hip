@@ -3,18 +3,16 @@
 // add_to_window (:1722-1783) and the run loop around them (:1914-1956) - with get_median_depth
 // (utils/slam_utils.py:286-297) of the frame's final tracking render, in three stream-ordered launches:
 //
-//   k_kf_pass<1>  blocks [0, bp): LDS histogram of bits 31..21 of the valid depths (depth > 0 && opacity > 0.95; NaN
-//                 fails both), merged into hist1 with integer atomics.  Blocks [bp, bp + bc): covisibility counts
+//   k_kf_pass<1>  blocks [0, bp): level 1 of the radix select (radix_select.h) of the lower median of the valid depths
+//                 (depth > 0 && opacity > 0.95; NaN fails both).  Blocks [bp, bp + bc): covisibility counts
 //                 |cur|, |row_w|, |cur & row_w| over the N Gaussians (4 per lane and step: an int4 of n_touched, a
 //                 uint32 of every row), one 33-int partial per workgroup.
-//   k_kf_pass<2>  every workgroup selects, from hist1, the bucket holding rank k = (n - 1) / 2 and the rank left
-//                 inside it, then histograms bits 20..10 of the depths in that bucket into hist2.
-//   k_kf_pass<3>  the same one level down (bits 9..0 into hist3); the workgroup that takes the last ticket selects
-//                 the final bucket - the lower median's bit pattern, exactly torch.median's value - sums the count
-//                 partials and evaluates the decision in one thread, in the reference's order of operations.
-// Positive fp32 values order like their uint32 bit patterns (+inf included), so three histogram levels (11/11/10 bits)
-// pin the exact element of rank k.  No grid-wide barrier, no spinning, no float atomics: two calls give bit-identical
-// records.  The scratch's histograms and ticket are zero on entry and are restored to zero by the last workgroup.
+//   k_kf_pass<2>  level 2: every workgroup repeats level 1's search, rank k = (n - 1) / 2.
+//   k_kf_pass<3>  level 3; the workgroup that takes the last ticket selects the final bucket - the lower median's bit
+//                 pattern, exactly torch.median's value - sums the count partials and evaluates the decision in one
+//                 thread, in the reference's order of operations.
+// No grid-wide barrier, no spinning, no float atomics: two calls give bit-identical records.  The scratch's histograms
+// and ticket are zero on entry and are restored to zero by the last workgroup.
 #include <hip/hip_runtime.h>
 #include <math.h>
 
@@ -27,7 +25,6 @@ namespace {
 
 constexpr int kKfThreads = 256;
 constexpr int kKfMaxBlocks = 256;
-constexpr int kHist1 = 2048, kHist2 = 2048, kHist3 = 1024;
 constexpr int kKfCounts = 1 + 2 * MGS_KF_MAX_WINDOW;   // |cur|, |row_w| x 16, |cur & row_w| x 16
 
 __device__ __forceinline__ bool depth_valid(float d, float o) { return d > 0.f && o > 0.95f; }
@@ -189,25 +186,16 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
     count_block(A, S, blockIdx.x - S.bp);
     return;
   }
-  __shared__ int s_hist[kHist1];
+  __shared__ int s_hist[kRadixHist1];
   __shared__ int s_scan[kKfThreads / 64];
-  __shared__ int s_sel[2][3];
-  constexpr int nb = PASS == 3 ? kHist3 : kHist1;
+  __shared__ int s_sel[3];
+  constexpr int nb = radix_level_buckets(PASS);
   for (int b = tid; b < nb; b += kKfThreads) s_hist[b] = 0;
   // prologue: the bucket (prefix) that holds the median rank
-  unsigned prefix = 0;
-  bool any = true;
-  if (PASS >= 2) {
-    block_select<kKfThreads, kHist1 / kKfThreads>(S.hist1, -1, s_scan, s_sel[0]);
-    any = s_sel[0][0] >= 0;
-    prefix = (unsigned)s_sel[0][0];
-    if (PASS == 3 && any) {
-      block_select<kKfThreads, kHist2 / kKfThreads>(S.hist2, s_sel[0][1], s_scan, s_sel[1]);
-      prefix = prefix << 11 | (unsigned)s_sel[1][0];
-    }
-  }
-  __syncthreads();
-  if (any) {
+  RadixSelected sel{0u, 0, 0, true};
+  if (PASS >= 2) sel = radix_select<kKfThreads>(S.hist, PASS - 1, LowerMedianRank{}, s_scan, s_sel);   // ends in a barrier
+  else __syncthreads();
+  if (sel.any) {
     const int HW = A.num_pixels, n4 = (HW + 3) >> 2;
     for (int q = blockIdx.x * kKfThreads + tid; q < n4; q += S.bp * kKfThreads) {
       float d[4], o[4];
@@ -227,31 +215,14 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
 #pragma unroll
       for (int j = 0; j < 4; j++) {
         const bool ok = depth_valid(d[j], o[j]);
-        const unsigned bits = __float_as_uint(d[j]);
-        if (PASS == 1) {
-          // a frame's depths share a few top-bit buckets: one LDS increment per distinct bucket and wave
-          const unsigned b = bits >> 21;
-          unsigned long long pending = __ballot(ok);
-          while (pending) {
-            const unsigned lb = (unsigned)__shfl((int)b, __ffsll((long long)pending) - 1);
-            const unsigned long long same = __ballot(ok && b == lb) & pending;
-            if (ok && b == lb && __ffsll((long long)same) - 1 == (int)(threadIdx.x & 63))
-              atomicAdd(&s_hist[lb], __popcll(same));
-            pending &= ~same;
-          }
-        }
-        if (!ok) continue;
-        if (PASS == 2 && (bits >> 21) == prefix) atomicAdd(&s_hist[(bits >> 10) & 2047u], 1);
-        if (PASS == 3 && (bits >> 10) == prefix) atomicAdd(&s_hist[bits & 1023u], 1);
+        const RadixBucket rb = radix_level<PASS>(__float_as_uint(d[j]), sel.prefix);
+        if (PASS == 1) radix_hist_add_aggregated(s_hist, ok, rb.bucket);
+        else if (ok && rb.counts) atomicAdd(&s_hist[rb.bucket], 1);
       }
     }
   }
   __syncthreads();
-  int* out = PASS == 1 ? S.hist1 : (PASS == 2 ? S.hist2 : S.hist3);
-  for (int b = tid; b < nb; b += kKfThreads) {
-    const int v = s_hist[b];
-    if (v) atomicAdd(&out[b], v);
-  }
+  radix_hist_flush<kKfThreads>(s_hist, S.hist.level(PASS), nb);
   if (PASS != 3) return;
   // ---- the last workgroup: the median's last bits, the counts, the decision; then the scratch is zeroed again
   // the barrier orders every lane's increments before lane 0's agent-scope release and ticket (as k_ssim_loss); one
@@ -265,11 +236,11 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
   }
   __syncthreads();
   if (!s_last) return;
-  const int n_valid = s_sel[0][2];
+  const int n_valid = sel.total;
   float med = __uint_as_float(0x7fc00000u);   // NaN: torch.median of an empty selection
-  if (any) {
-    block_select<kKfThreads, kHist3 / kKfThreads>(S.hist3, s_sel[1][1], s_scan, s_sel[1]);
-    med = __uint_as_float(prefix << 10 | (unsigned)s_sel[1][0]);
+  if (sel.any) {
+    block_select<kKfThreads, kRadixHist3 / kKfThreads>(S.hist.h3, sel.rank, s_scan, s_sel);
+    med = __uint_as_float(sel.prefix << 10 | (unsigned)s_sel[0]);
   }
   // count partials: thread t loads workgroup t's 33 ints (independent loads, bc <= 256), then wave and block sums
   __shared__ int s_part[kKfCounts][kKfThreads / 64];
@@ -301,11 +272,7 @@ __global__ __launch_bounds__(kKfThreads) void k_kf_pass(const mgs_keyframe_args 
   for (int e = tid; e < np * np; e += kKfThreads) s_rel[e / np][e % np] = rel_translation_norm(s_T[e / np], s_T[e % np]);
   __syncthreads();
   if (tid == 0) decide(A, s_cnt, n_valid, med, s_rel);
-  for (int b = tid; b < kHist1; b += kKfThreads) {
-    S.hist1[b] = 0;
-    S.hist2[b] = 0;
-  }
-  for (int b = tid; b < kHist3; b += kKfThreads) S.hist3[b] = 0;
+  for (int b = tid; b < kRadixHistInts; b += kKfThreads) S.hist.h1[b] = 0;   // the triple is contiguous
   if (tid == 0) *S.ticket = 0;
 }
 
@@ -321,9 +288,7 @@ KfLayout kf_layout(int num_gaussians, int num_pixels) {
   uint64_t o = 0;
   L.bp = blocks_for(num_pixels);
   L.bc = blocks_for(num_gaussians);
-  L.hist1 = o; o = align_up(o + (uint64_t)kHist1 * 4);
-  L.hist2 = o; o = align_up(o + (uint64_t)kHist2 * 4);
-  L.hist3 = o; o = align_up(o + (uint64_t)kHist3 * 4);
+  L.hists = o; o = align_up(o + (uint64_t)kRadixHistInts * 4);
   L.ticket = o; o = align_up(o + 4);
   L.partials = o; o = align_up(o + (uint64_t)L.bc * kKfCounts * 4);
   L.bytes = o;
@@ -334,9 +299,7 @@ int launch_keyframe_decide(const mgs_keyframe_args& A, hipStream_t st) {
   const KfLayout L = kf_layout(A.num_gaussians, A.num_pixels);
   char* w = static_cast<char*>(A.scratch);
   KfScratch S{};
-  S.hist1 = reinterpret_cast<int*>(w + L.hist1);
-  S.hist2 = reinterpret_cast<int*>(w + L.hist2);
-  S.hist3 = reinterpret_cast<int*>(w + L.hist3);
+  S.hist = radix_hists_at(w + L.hists);
   S.ticket = reinterpret_cast<int*>(w + L.ticket);
   S.partials = reinterpret_cast<int*>(w + L.partials);
   S.bp = L.bp;

@@ -28,6 +28,7 @@
 #include "launch.h"
 #include "radix_select.h"
 #include "raster_kernels.h"
+#include "rn_math.h"
 
 namespace mgs {
 
@@ -52,11 +53,9 @@ struct SeedState {
   unsigned all_lo;          // order key of the lower middle order statistic of d
 };
 
-struct SeedHists { int *h1, *h2, *h3; };
-
 struct SeedScratch {
   SeedState* state;
-  SeedHists prior, all, key;
+  RadixHists prior, all, key;
   double* moments;          // [kSeedMaxBlocks][2]
   int4* seg;                // [kSeedMaxSegments] (below, at, <= all_lo, order key of the smallest value above all_lo)
   float* d;                 // [H*W] the prepared depth map (depth_out when the caller gave one)
@@ -73,7 +72,7 @@ SeedLayout seed_layout(int num_pixels, int row_capacity) {
   SeedLayout L;
   uint64_t o = 0;
   L.state = o; o = align_up(o + sizeof(SeedState));
-  L.hists = o; o = align_up(o + 3ull * (kRadixHist1 + kRadixHist2 + kRadixHist3) * 4);
+  L.hists = o; o = align_up(o + 3ull * kRadixHistInts * 4);
   L.zero_bytes = o;
   L.moments = o; o = align_up(o + (uint64_t)kSeedMaxBlocks * 2 * sizeof(double));
   L.seg = o; o = align_up(o + (uint64_t)kSeedMaxSegments * sizeof(int4));
@@ -110,21 +109,6 @@ __device__ __forceinline__ unsigned draw_key(uint64_t seed, unsigned pixel) {
   return philox4x32_10(make_uint4(pixel, 0u, 1u, 0u), make_uint2((unsigned)seed, (unsigned)(seed >> 32))).x;
 }
 
-// Single roundings a torch mirror reproduces bit for bit.  HIP's __fmul_rn / __fadd_rn are plain operators, which the
-// default -ffp-contract=fast-honor-pragmas still fuses into an fma; the pragma takes the contract flag off these.
-__device__ __forceinline__ float mul_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a * b;
-}
-__device__ __forceinline__ float add_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a + b;
-}
-__device__ __forceinline__ float sub_rn(float a, float b) {
-#pragma clang fp contract(off)
-  return a - b;
-}
-
 // ---- small block-wide helpers -------------------------------------------------------------------------------------
 __device__ __forceinline__ bool valid_rgb(const mgs_keyframe_seed_args& A, int i, int HW) {
   return add_rn(add_rn(A.image[i], A.image[HW + i]), A.image[2 * (size_t)HW + i]) > A.rgb_boundary_threshold;
@@ -133,57 +117,6 @@ __device__ __forceinline__ bool valid_rgb(const mgs_keyframe_seed_args& A, int i
 __device__ __forceinline__ bool prior_valid(float d, float o, bool rgb) { return d > 0.f && o > 0.95f && rgb; }
 
 __device__ __forceinline__ bool depth_usable(float d, float trunc) { return d > 0.f && d <= trunc; }
-
-// One LDS increment per distinct bucket and wave: depth values share a few top-bit buckets.  All lanes call it.
-__device__ __forceinline__ void hist_add_aggregated(int* s_hist, bool ok, unsigned b) {
-  unsigned long long pending = __ballot(ok);
-  while (pending) {
-    const unsigned lb = (unsigned)__shfl((int)b, __ffsll((long long)pending) - 1);
-    const unsigned long long same = __ballot(ok && b == lb) & pending;
-    if (ok && b == lb && __ffsll((long long)same) - 1 == (int)(threadIdx.x & 63)) atomicAdd(&s_hist[lb], __popcll(same));
-    pending &= ~same;
-  }
-}
-
-__device__ __forceinline__ void hist_flush(const int* s_hist, int* out, int nb) {
-  for (int b = threadIdx.x; b < nb; b += kSeedThreads) {
-    const int v = s_hist[b];
-    if (v) atomicAdd(&out[b], v);
-  }
-}
-
-// The first `levels` levels of a select, repeated by every workgroup.  Returns false when no element has the rank.
-// out: prefix = the selected key's top bits (11, 22 or all 32), rank = the rank left inside that bucket, total.
-struct Selected { unsigned prefix; int rank, total; bool any; };
-template <class RankOf>
-__device__ Selected select_levels(const SeedHists& H, int levels, RankOf rank_of, int* s_scan, int* s_sel) {
-  Selected r;
-  block_select_by<kSeedThreads, kRadixHist1 / kSeedThreads>(H.h1, rank_of, s_scan, s_sel);
-  r.total = s_sel[2];
-  r.any = s_sel[0] >= 0;
-  r.prefix = (unsigned)s_sel[0];
-  r.rank = s_sel[1];
-  if (levels >= 2 && r.any) {
-    const int k2 = r.rank;
-    __syncthreads();
-    block_select<kSeedThreads, kRadixHist2 / kSeedThreads>(H.h2, k2, s_scan, s_sel);
-    r.prefix = r.prefix << 11 | (unsigned)s_sel[0];
-    r.rank = s_sel[1];
-    if (levels >= 3) {
-      const int k3 = r.rank;
-      __syncthreads();
-      block_select<kSeedThreads, kRadixHist3 / kSeedThreads>(H.h3, k3, s_scan, s_sel);
-      r.prefix = r.prefix << 10 | (unsigned)s_sel[0];
-      r.rank = s_sel[1];
-    }
-  }
-  __syncthreads();
-  return r;
-}
-
-struct LowerMedianRank {
-  __device__ int operator()(int total) const { return (total - 1) / 2; }   // torch.median's element; 0 when empty
-};
 
 // rank of the K-th smallest key, K = floor(n / downsample) as Python's int(n / downsample) (a double division)
 struct SubsampleRank {
@@ -199,11 +132,11 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_prior(const mgs_keyframe_
   __shared__ int s_scan[kSeedWaves];
   __shared__ int s_sel[3];
   const int tid = threadIdx.x, HW = A.width * A.height;
-  constexpr int nb = PASS == 3 ? kRadixHist3 : kRadixHist1;
+  constexpr int nb = radix_level_buckets(PASS);
   for (int b = tid; b < nb; b += kSeedThreads) s_hist[b] = 0;
-  Selected sel{0u, 0, 0, true};
-  if (PASS >= 2) sel = select_levels(S.prior, PASS - 1, LowerMedianRank{}, s_scan, s_sel);
-  __syncthreads();
+  RadixSelected sel{0u, 0, 0, true};
+  if (PASS >= 2) sel = radix_select<kSeedThreads>(S.prior, PASS - 1, LowerMedianRank{}, s_scan, s_sel);   // ends in a barrier
+  else __syncthreads();
   if (sel.any) {
     for (int base = blockIdx.x * kSeedStep; base < HW; base += gridDim.x * kSeedStep) {
 #pragma unroll
@@ -212,15 +145,14 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_prior(const mgs_keyframe_
         const bool in = i < HW;
         const float d = in ? A.depth[i] : 0.f;
         const bool ok = in && prior_valid(d, A.opacity[i], valid_rgb(A, i, HW));
-        const unsigned bits = __float_as_uint(d);
-        if (PASS == 1) hist_add_aggregated(s_hist, ok, bits >> 21);
-        if (PASS == 2 && ok && (bits >> 21) == sel.prefix) atomicAdd(&s_hist[(bits >> 10) & 2047u], 1);
-        if (PASS == 3 && ok && (bits >> 10) == sel.prefix) atomicAdd(&s_hist[bits & 1023u], 1);
+        const RadixBucket rb = radix_level<PASS>(__float_as_uint(d), sel.prefix);
+        if (PASS == 1) radix_hist_add_aggregated(s_hist, ok, rb.bucket);
+        else if (ok && rb.counts) atomicAdd(&s_hist[rb.bucket], 1);
       }
     }
   }
   __syncthreads();
-  hist_flush(s_hist, PASS == 1 ? S.prior.h1 : (PASS == 2 ? S.prior.h2 : S.prior.h3), nb);
+  radix_hist_flush<kSeedThreads>(s_hist, S.prior.level(PASS), nb);
 }
 
 // fp64 sums of (d - med) and (d - med)^2 over the valid depths: one partial per workgroup, summed lane tree -> wave
@@ -230,7 +162,7 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_moments(const mgs_keyfram
   __shared__ int s_sel[3];
   __shared__ double s_red[2][kSeedWaves];
   const int tid = threadIdx.x, HW = A.width * A.height;
-  const Selected sel = select_levels(S.prior, 3, LowerMedianRank{}, s_scan, s_sel);
+  const RadixSelected sel = radix_select<kSeedThreads>(S.prior, 3, LowerMedianRank{}, s_scan, s_sel);
   const float med = sel.any ? __uint_as_float(sel.prefix) : __uint_as_float(0x7fc00000u);
   double s1 = 0.0, s2 = 0.0;
   if (sel.total >= 2) {
@@ -335,8 +267,8 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_prepare(const mgs_keyfram
         S.d[i] = d;
         S.keys[i] = key;
       }
-      hist_add_aggregated(s_all, in, float_order_key(d) >> 21);
-      if (in && depth_usable(d, A.depth_trunc)) atomicAdd(&s_key[key >> 21], 1);
+      radix_hist_add_aggregated(s_all, in, radix_level<1>(float_order_key(d), 0u).bucket);
+      if (in && depth_usable(d, A.depth_trunc)) atomicAdd(&s_key[radix_level<1>(key, 0u).bucket], 1);
     }
   }
   if (A.mode == 0) {
@@ -349,8 +281,8 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_prepare(const mgs_keyfram
     for (int w = 0; w < kSeedWaves; w++) t += s_bad[w];
     if (t) atomicAdd(&S.state->n_outliers, t);
   }
-  hist_flush(s_all, S.all.h1, kRadixHist1);
-  hist_flush(s_key, S.key.h1, kRadixHist1);
+  radix_hist_flush<kSeedThreads>(s_all, S.all.h1, kRadixHist1);
+  radix_hist_flush<kSeedThreads>(s_key, S.key.h1, kRadixHist1);
 }
 
 // Levels 2 and 3 of both selects: the rank (H*W - 1) / 2 of the depth map's order keys, the rank K - 1 of the
@@ -362,30 +294,28 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_level(const mgs_keyframe_
   __shared__ int s_scan[kSeedWaves];
   __shared__ int s_sel[3];
   const int tid = threadIdx.x, HW = A.width * A.height;
-  constexpr int nb = PASS == 3 ? kRadixHist3 : kRadixHist1;
+  constexpr int nb = radix_level_buckets(PASS);
   for (int b = tid; b < nb; b += kSeedThreads) { s_all[b] = 0; s_key[b] = 0; }
-  const Selected sa = select_levels(S.all, PASS - 1, LowerMedianRank{}, s_scan, s_sel);
-  const Selected sk = select_levels(S.key, PASS - 1, SubsampleRank{A.downsample}, s_scan, s_sel);
-  __syncthreads();
+  const RadixSelected sa = radix_select<kSeedThreads>(S.all, PASS - 1, LowerMedianRank{}, s_scan, s_sel);
+  // ends in a barrier: both histograms are clear before any wave adds to them
+  const RadixSelected sk = radix_select<kSeedThreads>(S.key, PASS - 1, SubsampleRank{A.downsample}, s_scan, s_sel);
   for (int base = blockIdx.x * kSeedStep; base < HW; base += gridDim.x * kSeedStep) {
 #pragma unroll
     for (int j = 0; j < 4; j++) {
       const int i = base + j * kSeedThreads + tid;
       if (i >= HW) continue;
       const float d = S.d[i];
-      const unsigned m = float_order_key(d);
-      if (PASS == 2 && (m >> 21) == sa.prefix) atomicAdd(&s_all[(m >> 10) & 2047u], 1);
-      if (PASS == 3 && (m >> 10) == sa.prefix) atomicAdd(&s_all[m & 1023u], 1);
+      const RadixBucket ba = radix_level<PASS>(float_order_key(d), sa.prefix);
+      if (ba.counts) atomicAdd(&s_all[ba.bucket], 1);
       if (sk.any && depth_usable(d, A.depth_trunc)) {
-        const unsigned k = S.keys[i];
-        if (PASS == 2 && (k >> 21) == sk.prefix) atomicAdd(&s_key[(k >> 10) & 2047u], 1);
-        if (PASS == 3 && (k >> 10) == sk.prefix) atomicAdd(&s_key[k & 1023u], 1);
+        const RadixBucket bk = radix_level<PASS>(S.keys[i], sk.prefix);
+        if (bk.counts) atomicAdd(&s_key[bk.bucket], 1);
       }
     }
   }
   __syncthreads();
-  hist_flush(s_all, PASS == 2 ? S.all.h2 : S.all.h3, nb);
-  hist_flush(s_key, PASS == 2 ? S.key.h2 : S.key.h3, nb);
+  radix_hist_flush<kSeedThreads>(s_all, S.all.level(PASS), nb);
+  radix_hist_flush<kSeedThreads>(s_key, S.key.level(PASS), nb);
 }
 
 // Per wave segment: how many usable pixels lie below / at the key threshold; how many values are <= the lower middle
@@ -394,9 +324,9 @@ __global__ __launch_bounds__(kSeedThreads) void k_seed_count(const mgs_keyframe_
   __shared__ int s_scan[kSeedWaves];
   __shared__ int s_sel[3];
   const int tid = threadIdx.x, lane = tid & 63, HW = A.width * A.height;
-  const Selected sa = select_levels(S.all, 3, LowerMedianRank{}, s_scan, s_sel);
+  const RadixSelected sa = radix_select<kSeedThreads>(S.all, 3, LowerMedianRank{}, s_scan, s_sel);
   const SubsampleRank sub{A.downsample};
-  const Selected sk = select_levels(S.key, 3, sub, s_scan, s_sel);
+  const RadixSelected sk = radix_select<kSeedThreads>(S.key, 3, sub, s_scan, s_sel);
   if (blockIdx.x == 0 && tid == 0) {
     S.state->all_lo = sa.prefix;
     S.state->key_thr = sk.any ? sk.prefix : 0u;
@@ -564,12 +494,9 @@ int launch_keyframe_seed(const mgs_keyframe_seed_args& A, hipStream_t st) {
   SeedScratch S{};
   S.state = reinterpret_cast<SeedState*>(w + L.state);
   int* h = reinterpret_cast<int*>(w + L.hists);
-  SeedHists* hs[3] = {&S.prior, &S.all, &S.key};
-  for (SeedHists* x : hs) {
-    x->h1 = h; h += kRadixHist1;
-    x->h2 = h; h += kRadixHist2;
-    x->h3 = h; h += kRadixHist3;
-  }
+  S.prior = radix_hists_at(h);
+  S.all = radix_hists_at(h + kRadixHistInts);
+  S.key = radix_hists_at(h + 2 * kRadixHistInts);
   S.moments = reinterpret_cast<double*>(w + L.moments);
   S.seg = reinterpret_cast<int4*>(w + L.seg);
   S.d = A.depth_out ? A.depth_out : reinterpret_cast<float*>(w + L.d);

@@ -1,11 +1,13 @@
-// Rank selection over a device histogram, shared by the radix selects of keyframe_policy.hip (the median depth of
-// mgs_keyframe_decide) and keyframe_seed.hip (the depth prior's median, NumPy's median of the prepared depth map and
-// the K-th smallest sampling key of mgs_keyframe_seed).
+// The exact element of rank k of a plane of 32-bit keys: the one radix select of the library.  Its users:
+//   keyframe_policy.hip  the median depth of mgs_keyframe_decide;
+//   keyframe_seed.hip    the depth prior's median, NumPy's median of the prepared depth map and the K-th smallest
+//                        sampling key of mgs_keyframe_seed;
+//   frame_prepare.hip    the median gradient intensity of mgs_frame_prepare, over the image and per 32x32 patch.
 //
-// A select of 32-bit keys runs three histogram levels (bits 31..21, 20..10, 9..0: 2048 / 2048 / 1024 buckets); every
-// workgroup of the next level repeats the search of the previous level's histogram itself, so no grid-wide barrier
-// and no spinning is needed.  Positive fp32 values order like their uint32 bit patterns (+inf included);
-// float_order_key() extends that order to negative values.
+// A select runs three histogram levels (bits 31..21, 20..10, 9..0: 2048 / 2048 / 1024 buckets, radix_level); every
+// workgroup of the next level repeats the search of the earlier levels' histograms itself (radix_select), so no
+// grid-wide barrier and no spinning is needed.  Positive fp32 values order like their uint32 bit patterns (+inf
+// included); float_order_key() extends that order to negative values.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -60,18 +62,45 @@ __device__ void block_select(const int* hist, int k, int* s_scan, int* s_out) {
   block_select_by<THREADS, PER>(hist, [k](int total) { return k < 0 ? (total - 1) / 2 : k; }, s_scan, s_out);
 }
 
-// ---- the pieces of a three-level select over global histograms, for kernels of THREADS threads (frame_prepare.hip;
-// keyframe_seed.hip keeps its own, older copies) ---------------------------------------------------------------------
-struct RadixHists { int *h1, *h2, *h3; };
+// ---- the pieces of a three-level select over global histograms, for kernels of THREADS threads -------------------------
+constexpr int kRadixHistInts = kRadixHist1 + kRadixHist2 + kRadixHist3;   // ints of one histogram triple
 
-// The first `levels` levels of the select of the lower median, repeated by every workgroup.  prefix = the selected
-// key's top bits (11, 22 or all 32), rank = the rank left inside that bucket, total = the histogram's own total;
-// any = false when the histogram is empty.  s_scan holds THREADS / 64 ints, s_sel 3.  All threads call it.
+// The three histograms of one select: contiguous, h1 first (a memset or one loop over kRadixHistInts clears them).
+struct RadixHists {
+  int *h1, *h2, *h3;
+  __host__ __device__ int* level(int l) const { return l == 1 ? h1 : (l == 2 ? h2 : h3); }
+};
+inline RadixHists radix_hists_at(void* base) {
+  int* h = static_cast<int*>(base);
+  return RadixHists{h, h + kRadixHist1, h + kRadixHist1 + kRadixHist2};
+}
+constexpr int radix_level_buckets(int level) { return level == 1 ? kRadixHist1 : (level == 2 ? kRadixHist2 : kRadixHist3); }
+
+// Level LEVEL's rule for one key: does it count (its bits above the level equal the prefix selected so far) and in
+// which bucket.  Level 1 counts every key.
+struct RadixBucket { bool counts; unsigned bucket; };
+template <int LEVEL>
+__device__ __forceinline__ RadixBucket radix_level(unsigned key, unsigned prefix) {
+  static_assert(LEVEL >= 1 && LEVEL <= 3, "three levels");
+  if (LEVEL == 1) return RadixBucket{true, key >> 21};
+  if (LEVEL == 2) return RadixBucket{(key >> 21) == prefix, (key >> 10) & 2047u};
+  return RadixBucket{(key >> 10) == prefix, key & 1023u};
+}
+
+// torch.median's element: the lower-median rank of the histogram's own total (0 when it is empty).
+struct LowerMedianRank {
+  __device__ int operator()(int total) const { return (total - 1) / 2; }
+};
+
+// The first `levels` levels of the select of rank rank_of(level 1's total), repeated by every workgroup.  prefix = the
+// selected key's top bits (11, 22 or all 32), rank = the rank left inside that bucket, total = level 1's total;
+// any = false when no element has the rank (an empty histogram, a negative rank): prefix and rank mean nothing then.
+// s_scan holds THREADS / 64 ints, s_sel 3.  All threads call it; it ends in a barrier.
 struct RadixSelected { unsigned prefix; int rank, total; bool any; };
-template <int THREADS>
-__device__ RadixSelected radix_select_median(const RadixHists& H, int levels, int* s_scan, int* s_sel) {
+template <int THREADS, class RankOf>
+__device__ RadixSelected radix_select(const RadixHists& H, int levels, RankOf rank_of, int* s_scan, int* s_sel) {
   RadixSelected r;
-  block_select<THREADS, kRadixHist1 / THREADS>(H.h1, -1, s_scan, s_sel);
+  block_select_by<THREADS, kRadixHist1 / THREADS>(H.h1, rank_of, s_scan, s_sel);
   r.total = s_sel[2];
   r.any = s_sel[0] >= 0;
   r.prefix = (unsigned)s_sel[0];
@@ -94,7 +123,8 @@ __device__ RadixSelected radix_select_median(const RadixHists& H, int levels, in
   return r;
 }
 
-// One LDS increment per distinct bucket and wave: image statistics share a few top-bit buckets.  All lanes call it.
+// One LDS increment per distinct bucket and wave: depths and image statistics share a few top-bit buckets.  All lanes
+// call it.
 __device__ __forceinline__ void radix_hist_add_aggregated(int* s_hist, bool ok, unsigned b) {
   unsigned long long pending = __ballot(ok);
   while (pending) {

@@ -5,6 +5,7 @@
 #include <stdint.h>
 
 #include "../../include/monogs_raster.h"
+#include "radix_select.h"
 #include "raster_math.h"
 
 // Traffic ablations (variant builds of profiles/tools/build_variant.sh only; the product is built without them):
@@ -244,13 +245,13 @@ int launch_sampled_pose(const KP& P, const KS& S, hipStream_t st);
 
 // Keyframe policy (keyframe_policy.hip, mgs_keyframe_decide): scratch views and grid of the three launches.
 struct KfScratch {
-  int *hist1, *hist2, *hist3;   // [2048] [2048] [1024] radix histograms: zero on entry, zeroed again by the last block
+  RadixHists hist;              // the select's histograms: zero on entry, zeroed again by the last block
   int* ticket;                  // zero on entry, likewise
   int* partials;                // [bc][33] per-workgroup covisibility counts
   int bp, bc;                   // pixel workgroups, count workgroups
   int vec_pixels, vec_touched, vec_rows;   // 16-B aligned depth / opacity, 16-B n_touched, 4-B rows
 };
-struct KfLayout { uint64_t hist1, hist2, hist3, ticket, partials, bytes; int bp, bc; };
+struct KfLayout { uint64_t hists, ticket, partials, bytes; int bp, bc; };
 KfLayout kf_layout(int num_gaussians, int num_pixels);
 int launch_keyframe_decide(const mgs_keyframe_args& A, hipStream_t st);
 

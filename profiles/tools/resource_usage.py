@@ -11,7 +11,7 @@ CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "..", "mon
 files = [a for a in sys.argv[1:] if a.endswith(".hip")] or ["raster_forward.hip", "raster_backward.hip", "tracking.hip",
                                                            "map_update.hip", "knn.hip"]
 flags = [a for a in sys.argv[1:] if not a.endswith(".hip")]
-KEYS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("SGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"),
+KEYS = (("VGPRs", "vgpr"), ("AGPRs", "agpr"), ("TotalSGPRs", "sgpr"), ("ScratchSize [bytes/lane]", "scratch"),
         ("Occupancy [waves/SIMD]", "occ"), ("LDS Size [bytes/block]", "lds"))
 for f in files:
     r = subprocess.run(["/opt/rocm/bin/hipcc", "-O3", "-fno-slp-vectorize", "--offload-arch=gfx950", "-std=c++17", "-c", f,
@@ -28,7 +28,7 @@ for f in files:
             flush()
             name = subprocess.run(["c++filt", m.group(1)], capture_output=True,
                                   text=True).stdout.strip() or m.group(1)
-            name = re.sub(r"\(.*$", "", re.sub(r"^void mgs::", "", name))
+            name = re.sub(r"\(.*$", "", re.sub(r"^(void )?mgs::", "", name.replace("(anonymous namespace)::", "")))
             row = {}
             continue
         m = re.search(r"remark: [^:]*:\d+:\d+:\s+([A-Za-z][^:]*): (\d+)", line) or re.search(r"remark:\s+.*?([A-Z][A-Za-z \[\]/]+): (\d+)", line)

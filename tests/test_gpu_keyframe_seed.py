@@ -137,6 +137,90 @@ def test_median_all_edge_cases(built):
         assert r.n_depth == n and r.num_points == n // 2
 
 
+TIE_KEY = 0x40000000
+SELECT_EDGE_CASES = ("ties_at_threshold", "all_keys_equal", "prior_0_valid", "prior_1_valid", "prior_2_valid",
+                     "no_depth_zero", "no_depth_beyond_trunc", "downsample_1")
+
+
+@pytest.mark.parametrize("case", SELECT_EDGE_CASES)
+def test_select_outputs_at_their_edges(built, case):
+    """Where the radix select's rank, `any` and total decide the result: sampling keys tied at the K-th smallest (the
+    ties cross wave segments: 53 x 75 is 63 segments of 64 pixels), one key for every pixel, a depth prior of 0 / 1 / 2
+    valid pixels, no usable depth at all, and K = n (the rank is the last element)."""
+    H, W = (5, 7) if case == "downsample_1" else (53, 75)
+    ds = 1 if case == "downsample_1" else 2
+    g = torch.Generator().manual_seed(len(case) + H)
+    cam = make_cam(H, W, DEV)
+    image = torch.full((3, H, W), 0.5)
+    depth = 0.5 + 3 * torch.rand(H, W, generator=g)
+    noise = torch.randn(H, W, generator=g)
+    keys = torch.randint(0, 2 ** 32, (H * W,), generator=g, dtype=torch.int64)
+    S = KS.KeyframeSeeder(H, W, DEV, config(downsample=ds, downsample_init=ds))
+
+    if case.startswith("prior_"):
+        n = int(case.split("_")[1])
+        image[:, :4, :] = 0.0                              # no image content: never valid, depth 0 afterwards
+        opacity = torch.full((H, W), 0.5)
+        opacity[2, 9] = 0.99                               # opaque, but without image content
+        for y, x in ((7, 70), (40, 3))[:n]:                # in different wave segments
+            opacity[y, x] = 0.99
+        image, depth, opacity, noise = (t.to(DEV) for t in (image, depth, opacity, noise))
+        r = S.seed(cam, image, depth, opacity, KS.MODE_RENDERED, False, seed=1, noise=noise, keys=keys)[-1]
+        d, info = KS.depth_prior_torch(image, depth, opacity, KS.MODE_RENDERED, noise)
+        assert info["n_valid"] == n and r.n_valid == n
+        if n == 0:
+            assert math.isnan(r.median_depth)
+        else:
+            assert f32_bits(r.median_depth) == f32_bits(info["median_depth"].item())
+        if n < 2:
+            assert math.isnan(r.std_depth)
+        else:
+            # two values: both sides hold the same exact fp64 sums, so only the fp64 square root and the one rounding
+            # to fp32 can differ
+            want = info["std_depth"].item()
+            print(f"std native {r.std_depth:.9g} mirror {want:.9g}")
+            assert abs(r.std_depth - want) <= EPS * want
+        assert torch.equal(S.depth_out, d)
+        usable = int(((d > 0) & (d <= 100)).sum())
+        assert r.n_depth == usable and r.num_points == usable // ds
+        return
+
+    if case == "no_depth_zero":
+        depth = torch.zeros(H, W)
+    if case == "no_depth_beyond_trunc":
+        depth = depth + 150.0
+    if case in ("ties_at_threshold", "all_keys_equal", "downsample_1"):
+        depth.view(-1)[torch.randperm(H * W, generator=g)[: max(2, H * W // 5)]] = 0.0
+    if case == "ties_at_threshold":
+        keys[torch.rand(H * W, generator=g) < 0.5] = TIE_KEY
+    if case == "all_keys_equal":
+        keys[:] = TIE_KEY
+    image, depth = image.to(DEV), depth.to(DEV)
+    out = S.seed(cam, image, depth, None, KS.MODE_SENSOR, False, seed=1, keys=keys)      # raises unless the call is OK
+    r = out[-1]
+    want_med = np.median(depth.cpu().numpy())
+    assert f32_bits(r.median_all) == f32_bits(want_med)
+    flat = depth.reshape(-1).cpu()
+    usable = (flat > 0) & (flat <= 100)
+    n = int(usable.sum())
+    K = int(n / ds)
+    assert r.n_depth == n and r.num_points == K == out[0].shape[0]
+    if case.startswith("no_depth"):
+        assert n == 0 and K == 0
+        return
+    sel, n_sel = KS.select_torch(depth, keys, ds)
+    assert n_sel == n and sel.numel() == K > 0
+    if case == "ties_at_threshold":
+        below, upto = int((keys[usable] < TIE_KEY).sum()), int((keys[usable] <= TIE_KEY).sum())
+        print(f"usable {n}, K {K}, keys below the tie {below}, up to it {upto}")
+        assert below < K <= upto
+    if case == "all_keys_equal":
+        assert torch.equal(sel.cpu(), torch.nonzero(usable).reshape(-1)[:K])          # the first K in pixel order
+    if case == "downsample_1":
+        assert K == n < H * W
+    assert torch.equal(S.pixel_index[:K].long(), sel)
+
+
 @pytest.mark.parametrize("downsample,holes", [(64, False), (32, False), (64, True)])
 def test_replica_shape_scales_against_the_oracle(built, downsample, holes):
     """1200x680 sensor depth: 12 750 / 25 500 points take k_knn_partial<2> / <4>; the hole pattern makes the count a
