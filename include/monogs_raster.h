@@ -840,6 +840,70 @@ uint64_t mgs_frame_prepare_scratch_bytes(int32_t H, int32_t W);
  * Global mode: one memset node and four launches; patch mode: one launch.  No host read, no synchronisation. */
 int32_t mgs_frame_prepare(const mgs_frame_prepare_args* args, void* stream);
 
+/* ---- undistortion / rectification fused into frame preparation (DESIGN.md "Undistort and rectify") ---------------
+ * What the reference's dataset does to a frame before anything else sees it when Calibration.distorted is set:
+ * cv2.remap(image, map1x, map1y, INTER_LINEAR) with the maps of cv2.initUndistortRectifyMap (utils/dataset.py:226-244,
+ * 264-265).  Here the gather is fused into the tile load of mgs_frame_prepare: no launch and no pass over the image is
+ * added.  Parity with cv2 is UNPINNED (no cv2 to produce a fixture with); the contract below is this library's own, and
+ * kernel and mirror (frame_prepare.remap_build_numpy / remap_torch) agree bit for bit, so the order of operations is
+ * part of it.
+ *
+ * Map build, once per calibration; all arithmetic fp64, no contraction, in this order.  ir[9]: the row-major inverse of
+ * new_K * R, computed by the caller in double (nothing is inverted on the device); fx, fy, cx, cy: the source
+ * (distorted) camera; dist = (k1, k2, p1, p2, k3), OpenCV's order.  For destination pixel (u, v):
+ *   X = (ir0*u + ir1*v) + ir2;  Y = (ir3*u + ir4*v) + ir5;  Wd = (ir6*u + ir7*v) + ir8
+ *   x = X / Wd;  y = Y / Wd
+ *   x2 = x*x;  y2 = y*y;  r2 = x2 + y2;  txy = (2*x)*y
+ *   kr = 1 + ((k3*r2 + k2)*r2 + k1)*r2
+ *   xd = (x*kr + p1*txy) + p2*(r2 + 2*x2)
+ *   yd = (y*kr + p1*(r2 + 2*y2)) + p2*txy
+ *   mx = float32(fx*xd + cx);  my = float32(fy*yd + cy)
+ *   ix = rint_half_even(double(mx) * 32) clamped to [-2^30, 2^30];  iy likewise
+ * mx or my not finite: ix = iy = -2^30 (every tap falls outside the image).  The map is int32 [H][W][2] holding
+ * (ix, iy): the source position in 1/32-pixel fixed point.
+ *
+ * Remap, for each destination pixel and each reflect-padded halo pixel (the halo of destination (y, x) reads the map at
+ * (reflect(y), reflect(x)): padding happens on the undistorted image).  sx = ix >> 5, sy = iy >> 5 (arithmetic shifts);
+ * ax = ix & 31, ay = iy & 31; the taps are (sy,sx), (sy,sx+1), (sy+1,sx), (sy+1,sx+1); a tap outside [0,H) x [0,W)
+ * reads 0 in every channel, decided per tap (a constant border).  Integer weights w00 = (32-ax)(32-ay),
+ * w01 = ax(32-ay), w10 = (32-ax)ay, w11 = ax*ay (they sum to 1024).
+ *   uint8 image  k = (w00*v00 + w01*v01 + w10*v10 + w11*v11 + 512) >> 10, then float32(k / 255.0).
+ *   float image  (f00*v00 + f01*v01) + (f10*v10 + f11*v11) with f = float(w) / 1024 (exact); every product and sum
+ *                rounded on its own (no fma).
+ * Everything downstream (sum, grey, gradient, medians, masks) is mgs_frame_prepare's contract on the remapped image.
+ *
+ * Depth.  MGS_FRAME_REMAP_DEPTH_NONE: gt_depth exactly as mgs_frame_prepare leaves it (the reference remaps the image
+ * only).  MGS_FRAME_REMAP_DEPTH_NEAREST: gt_depth = the tap ((iy+16) >> 5, (ix+16) >> 5) of the converted source depth,
+ * 0 outside - for callers who want depth and image registered (not the reference's behaviour). */
+#define MGS_FRAME_REMAP_DEPTH_NONE 0
+#define MGS_FRAME_REMAP_DEPTH_NEAREST 1
+
+typedef struct mgs_remap_build_args {
+  int32_t width, height;           /* the destination image; both >= 1 */
+  double ir[9];                    /* row-major inverse of new_K * R */
+  double fx, fy, cx, cy;           /* the source (distorted) camera */
+  double dist[5];                  /* k1, k2, p1, p2, k3 */
+  int32_t* map_q5;                 /* device int32 [H][W][2], 8-byte aligned: (ix, iy) per destination pixel */
+} mgs_remap_build_args;
+
+typedef struct mgs_frame_remap_args {
+  const int32_t* map_q5;           /* device int32 [H][W][2] of the frame's size, 8-byte aligned */
+  int32_t depth_mode;              /* MGS_FRAME_REMAP_DEPTH_* */
+  int32_t reserved0;
+} mgs_frame_remap_args;
+
+int32_t mgs_remap_build_args_size(void);
+int32_t mgs_frame_remap_args_size(void);
+/* One launch (k_fp_remap_build, a thread per destination pixel).  A null struct or map, a map that is not 8-byte
+ * aligned, a side < 1: MGS_ERR_BAD_ARGUMENT; more than 2^31 - 1 pixels: MGS_ERR_UNSUPPORTED. */
+int32_t mgs_remap_build(const mgs_remap_build_args* args, void* stream);
+/* mgs_frame_prepare on the remapped image: the same stream operations (global mode: one memset node and four launches,
+ * patch mode: one launch).  Everything mgs_frame_prepare checks, and MGS_ERR_BAD_ARGUMENT for: a null remap struct or
+ * map; a map that is not 8-byte aligned; an unknown depth_mode; a null `image`; image == image_in (either format: a
+ * gather cannot run in place); with MGS_FRAME_REMAP_DEPTH_NEAREST no depth, a null gt_depth or gt_depth == depth_in.
+ * Checked before anything is launched or written. */
+int32_t mgs_frame_prepare_remapped(const mgs_frame_prepare_args* args, const mgs_frame_remap_args* remap, void* stream);
+
 /* ---- map maintenance on the device ---------------------------------- */
 
 #define MGS_ADAM_MAX_GROUPS 8

@@ -31,6 +31,7 @@ EXPORTS = (
     "mgs_sketch_residual_rgbd", "mgs_tracking_sample_scratch_bytes", "mgs_tracking_iteration_sampled",
     "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide", "mgs_keyframe_seed_scratch_bytes", "mgs_keyframe_seed",
     "mgs_frame_prepare_args_size", "mgs_frame_prepare_scratch_bytes", "mgs_frame_prepare",
+    "mgs_remap_build_args_size", "mgs_frame_remap_args_size", "mgs_remap_build", "mgs_frame_prepare_remapped",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -268,6 +269,18 @@ class FramePrepareArgs(C.Structure):
                                       "rgb_pixel_mask_mapping", "median_out", "intensity_out", "scratch")])
 
 
+FRAME_REMAP_DEPTH_NONE, FRAME_REMAP_DEPTH_NEAREST = 0, 1
+
+
+class RemapBuildArgs(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("ir", C.c_double * 9), ("fx", C.c_double),
+                ("fy", C.c_double), ("cx", C.c_double), ("cy", C.c_double), ("dist", C.c_double * 5), ("map_q5", _fp)]
+
+
+class FrameRemapArgs(C.Structure):
+    _fields_ = [("map_q5", _fp), ("depth_mode", C.c_int32), ("reserved0", C.c_int32)]
+
+
 _lib = None
 
 
@@ -403,6 +416,14 @@ def lib():
     L.mgs_frame_prepare_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     L.mgs_frame_prepare.restype = C.c_int32
     L.mgs_frame_prepare.argtypes = [C.POINTER(FramePrepareArgs), C.c_void_p]
+    for fn, cls in ((L.mgs_remap_build_args_size, RemapBuildArgs), (L.mgs_frame_remap_args_size, FrameRemapArgs)):
+        fn.restype, fn.argtypes = C.c_int32, []
+        if fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    L.mgs_remap_build.restype = C.c_int32
+    L.mgs_remap_build.argtypes = [C.POINTER(RemapBuildArgs), C.c_void_p]
+    L.mgs_frame_prepare_remapped.restype = C.c_int32
+    L.mgs_frame_prepare_remapped.argtypes = [C.POINTER(FramePrepareArgs), C.POINTER(FrameRemapArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -13,6 +13,11 @@
 //                      of rank 511 of the tile's 1024 intensities by a three-level radix select in LDS, and the masks;
 //                      a tile that is no whole patch (the fringe fold() leaves at 0) gets grad_mask = 0
 //
+//   remapped (mgs_frame_prepare_remapped): the same operations with k_fp_intensity<true> / k_fp_patch<true>, whose tile
+//                      load gathers every pixel (halo included) bilinearly through a 1/32-pixel fixed-point map - the
+//                      reference's cv2.remap undistortion (utils/dataset.py:226-244,264-265).  k_fp_remap_build makes
+//                      that map once per calibration, in fp64.
+//
 // A latency problem (3.7 MB of float planes at 640x480): every launch is one resident round of workgroups.  Counting is
 // integer, nothing is summed in floating point across threads: two calls give bit-identical outputs.  No host read.
 #include <hip/hip_runtime.h>
@@ -62,23 +67,98 @@ __device__ __forceinline__ int reflect(int i, int n) {
   return min(max(r, 0), n - 1);
 }
 
+// What a kernel takes: the frame's arguments and, in the remapped instantiation, the map's.  FpArgs<false> is laid out
+// as mgs_frame_prepare_args itself.
+template <bool REMAP>
+struct FpArgs { mgs_frame_prepare_args a; };
+template <>
+struct FpArgs<true> { mgs_frame_prepare_args a; mgs_frame_remap_args r; };
+
+constexpr int kFpMapClamp = 1 << 30;   // |ix|, |iy| <= 2^30: ix + 32 and ix + 16 stay inside int32
+
+// One destination pixel's four taps (header: "Remap"): offsets into an [H][W] plane, -1 for a tap outside the image -
+// the bounds are checked before an address is formed - and the integer weights.
+struct FpTaps {
+  int2 q;                                                          // the map entry (ix, iy) itself
+  int64_t o00, o01, o10, o11;
+  int w00, w01, w10, w11;
+};
+
+__device__ __forceinline__ FpTaps remap_taps(const int32_t* map_q5, size_t p, int H, int W) {
+  const int2 q = reinterpret_cast<const int2*>(map_q5)[p];        // (ix, iy): one 8-byte load
+  const int sx = q.x >> 5, sy = q.y >> 5, ax = q.x & 31, ay = q.y & 31;
+  const bool x0 = sx >= 0 && sx < W, x1 = sx >= -1 && sx < W - 1;
+  const bool y0 = sy >= 0 && sy < H, y1 = sy >= -1 && sy < H - 1;
+  FpTaps t;
+  t.q = q;
+  t.o00 = y0 && x0 ? (int64_t)sy * W + sx : -1;
+  t.o01 = y0 && x1 ? (int64_t)sy * W + (sx + 1) : -1;
+  t.o10 = y1 && x0 ? (int64_t)(sy + 1) * W + sx : -1;
+  t.o11 = y1 && x1 ? (int64_t)(sy + 1) * W + (sx + 1) : -1;
+  t.w00 = (32 - ax) * (32 - ay);
+  t.w01 = ax * (32 - ay);
+  t.w10 = (32 - ax) * ay;
+  t.w11 = ax * ay;
+  return t;
+}
+
+__device__ __forceinline__ int tap_u8(const uint8_t* u, int64_t o, int c) { return o >= 0 ? (int)u[3 * o + c] : 0; }
+__device__ __forceinline__ float tap_f32(const float* f, int64_t o) { return o >= 0 ? f[o] : 0.f; }
+
+__device__ __forceinline__ float blend_u8(const FpTaps& t, const uint8_t* u, int c, const float* s_lut) {
+  const int k = (t.w00 * tap_u8(u, t.o00, c) + t.w01 * tap_u8(u, t.o01, c) + t.w10 * tap_u8(u, t.o10, c) +
+                 t.w11 * tap_u8(u, t.o11, c) + 512) >> 10;
+  return s_lut[k];
+}
+
+__device__ __forceinline__ float blend_f32(const FpTaps& t, const float* f) {
+#pragma clang fp contract(off)
+  const float f00 = (float)t.w00 * 0.0009765625f, f01 = (float)t.w01 * 0.0009765625f;     // w / 1024: exact
+  const float f10 = (float)t.w10 * 0.0009765625f, f11 = (float)t.w11 * 0.0009765625f;
+  return (f00 * tap_f32(f, t.o00) + f01 * tap_f32(f, t.o01)) + (f10 * tap_f32(f, t.o10) + f11 * tap_f32(f, t.o11));
+}
+
+__device__ __forceinline__ float convert_depth(const mgs_frame_prepare_args& A, size_t p) {
+  return A.depth_format == MGS_FRAME_DEPTH_U16
+             ? (float)((double)static_cast<const uint16_t*>(A.depth_in)[p] / A.depth_scale)
+             : static_cast<const float*>(A.depth_in)[p];
+}
+
 // The (TW + 2) x (TH + 2) channel sums and greys around the tile at (x0, y0) into LDS; the pixels of the tile itself
 // also get their converted image / depth written.  s_lut: k -> (float)(k / 255.0).  All threads call it.
-template <int TW, int TH>
-__device__ void load_tile(const mgs_frame_prepare_args& A, int x0, int y0, const float* s_lut, float* s_sum,
-                          float* s_grey) {
+// REMAP: every pixel, halo included, is gathered through the map at its reflected position.
+template <int TW, int TH, bool REMAP>
+__device__ void load_tile(const FpArgs<REMAP>& F, int x0, int y0, const float* s_lut, float* s_sum, float* s_grey) {
   constexpr int P = TW + 2;
+  const mgs_frame_prepare_args& A = F.a;
   const int H = A.height, W = A.width;
   const size_t HW = (size_t)H * W;
   const bool u8 = A.image_format == MGS_FRAME_IMAGE_U8_HWC;
-  const bool copy_image = A.image && (const void*)A.image != A.image_in;
+  const bool copy_image = REMAP || (A.image && (const void*)A.image != A.image_in);
   const bool copy_depth = A.depth_format != MGS_FRAME_DEPTH_NONE && A.gt_depth && (const void*)A.gt_depth != A.depth_in;
+  bool nearest = false;
+  if constexpr (REMAP) nearest = F.r.depth_mode == MGS_FRAME_REMAP_DEPTH_NEAREST;
   for (int t = threadIdx.x; t < P * (TH + 2); t += kFpThreads) {
     const int ty = t / P, tx = t - ty * P;
     const int y = y0 + ty - 1, x = x0 + tx - 1;
     const size_t p = (size_t)reflect(y, H) * W + reflect(x, W);
     float r, g, b;
-    if (u8) {
+    int2 q = make_int2(0, 0);                                      // REMAP: the pixel's map entry
+    if constexpr (REMAP) {
+      const FpTaps taps = remap_taps(F.r.map_q5, p, H, W);
+      q = taps.q;
+      if (u8) {
+        const uint8_t* u = static_cast<const uint8_t*>(A.image_in);
+        r = blend_u8(taps, u, 0, s_lut);
+        g = blend_u8(taps, u, 1, s_lut);
+        b = blend_u8(taps, u, 2, s_lut);
+      } else {
+        const float* f = static_cast<const float*>(A.image_in);
+        r = blend_f32(taps, f);
+        g = blend_f32(taps, f + HW);
+        b = blend_f32(taps, f + 2 * HW);
+      }
+    } else if (u8) {
       const uint8_t* u = static_cast<const uint8_t*>(A.image_in) + 3 * p;
       r = s_lut[u[0]];
       g = s_lut[u[1]];
@@ -98,10 +178,11 @@ __device__ void load_tile(const mgs_frame_prepare_args& A, int x0, int y0, const
         A.image[HW + p] = g;
         A.image[2 * HW + p] = b;
       }
-      if (copy_depth) {
-        A.gt_depth[p] = A.depth_format == MGS_FRAME_DEPTH_U16
-                            ? (float)((double)static_cast<const uint16_t*>(A.depth_in)[p] / A.depth_scale)
-                            : static_cast<const float*>(A.depth_in)[p];
+      if (REMAP && nearest) {                                      // the nearest source pixel of the converted depth
+        const int dx = (q.x + 16) >> 5, dy = (q.y + 16) >> 5;
+        A.gt_depth[p] = dx >= 0 && dx < W && dy >= 0 && dy < H ? convert_depth(A, (size_t)dy * W + dx) : 0.f;
+      } else if (copy_depth) {
+        A.gt_depth[p] = convert_depth(A, p);
       }
     }
   }
@@ -131,8 +212,10 @@ __device__ __forceinline__ void fill_lut(float* s_lut) {
 }
 
 // ---- global mode ------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(kFpThreads) void k_fp_intensity(const mgs_frame_prepare_args A, const FpScratch S) {
+template <bool REMAP>
+__global__ __launch_bounds__(kFpThreads) void k_fp_intensity(const FpArgs<REMAP> F, const FpScratch S) {
   constexpr int P = kFpTileW + 2;
+  const mgs_frame_prepare_args& A = F.a;
   __shared__ float s_lut[256];
   __shared__ float s_sum[P * (kFpTileH + 2)];
   __shared__ float s_grey[P * (kFpTileH + 2)];
@@ -142,7 +225,7 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_intensity(const mgs_frame_pre
   for (int b = tid; b < kRadixHist1; b += kFpThreads) s_hist[b] = 0;
   __syncthreads();
   const int x0 = blockIdx.x * kFpTileW, y0 = blockIdx.y * kFpTileH;
-  load_tile<kFpTileW, kFpTileH>(A, x0, y0, s_lut, s_sum, s_grey);
+  load_tile<kFpTileW, kFpTileH, REMAP>(F, x0, y0, s_lut, s_sum, s_grey);
   __syncthreads();
   const int tx = tid & 63, x = x0 + tx;
 #pragma unroll
@@ -227,8 +310,10 @@ __device__ __forceinline__ void patch_select_level(const float (&I)[PER], int* s
   __syncthreads();   // s_sel is read before the next level's search writes it
 }
 
-__global__ __launch_bounds__(kFpThreads) void k_fp_patch(const mgs_frame_prepare_args A) {
+template <bool REMAP>
+__global__ __launch_bounds__(kFpThreads) void k_fp_patch(const FpArgs<REMAP> F) {
   constexpr int P = kFpPatch + 2, PER = kFpPatch * kFpPatch / kFpThreads;
+  const mgs_frame_prepare_args& A = F.a;
   __shared__ float s_lut[256];
   __shared__ float s_sum[P * P];
   __shared__ float s_grey[P * P];
@@ -239,7 +324,7 @@ __global__ __launch_bounds__(kFpThreads) void k_fp_patch(const mgs_frame_prepare
   fill_lut(s_lut);
   __syncthreads();
   const int x0 = blockIdx.x * kFpPatch, y0 = blockIdx.y * kFpPatch;
-  load_tile<kFpPatch, kFpPatch>(A, x0, y0, s_lut, s_sum, s_grey);
+  load_tile<kFpPatch, kFpPatch, REMAP>(F, x0, y0, s_lut, s_sum, s_grey);
   __syncthreads();
   const bool whole = x0 + kFpPatch <= W && y0 + kFpPatch <= H;   // the same for the whole workgroup
   const int tx = tid & (kFpPatch - 1), x = x0 + tx;
@@ -297,11 +382,25 @@ int32_t frame_prepare_args_status(const mgs_frame_prepare_args* a) {
   return MGS_OK;
 }
 
-int launch_frame_prepare(const mgs_frame_prepare_args& A, hipStream_t st) {
+int32_t frame_remap_args_status(const mgs_frame_prepare_args* a, const mgs_frame_remap_args* r) {
+  if (!r || !r->map_q5 || (reinterpret_cast<uintptr_t>(r->map_q5) & 7u)) return MGS_ERR_BAD_ARGUMENT;
+  if (r->depth_mode != MGS_FRAME_REMAP_DEPTH_NONE && r->depth_mode != MGS_FRAME_REMAP_DEPTH_NEAREST)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (!a->image || (const void*)a->image == a->image_in) return MGS_ERR_BAD_ARGUMENT;    // a gather cannot run in place
+  if (r->depth_mode == MGS_FRAME_REMAP_DEPTH_NEAREST &&
+      (a->depth_format == MGS_FRAME_DEPTH_NONE || !a->gt_depth || (const void*)a->gt_depth == a->depth_in))
+    return MGS_ERR_BAD_ARGUMENT;
+  return MGS_OK;
+}
+
+template <bool REMAP>
+int launch_frame_prepare(const FpArgs<REMAP>& F, hipStream_t st) {
+  const mgs_frame_prepare_args& A = F.a;
   const int H = A.height, W = A.width, HW = H * W;
   const dim3 block(kFpThreads);
   if (A.mode == MGS_FRAME_MODE_PATCH) {
-    launch("fp_patch", k_fp_patch, dim3((W + kFpPatch - 1) / kFpPatch, (H + kFpPatch - 1) / kFpPatch), block, st, A);
+    launch("fp_patch", k_fp_patch<REMAP>, dim3((W + kFpPatch - 1) / kFpPatch, (H + kFpPatch - 1) / kFpPatch), block, st,
+           F);
     return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
   }
   const FpLayout L = fp_layout((uint64_t)HW);
@@ -313,11 +412,39 @@ int launch_frame_prepare(const mgs_frame_prepare_args& A, hipStream_t st) {
   hb = hb > kFpMaxBlocks ? kFpMaxBlocks : hb;
   const dim3 tiles((W + kFpTileW - 1) / kFpTileW, (H + kFpTileH - 1) / kFpTileH), hgrid(hb);
   if (!hip_ok("frame prepare memset", hipMemsetAsync(w, 0, L.zero_bytes, st))) { launches_ok(); return MGS_ERR_LAUNCH; }
-  launch("fp_intensity", k_fp_intensity, tiles, block, st, A, S);
+  launch("fp_intensity", k_fp_intensity<REMAP>, tiles, block, st, F, S);
   launch("fp_level2", k_fp_level<2>, hgrid, block, st, S, HW);
   launch("fp_level3", k_fp_level<3>, hgrid, block, st, S, HW);
   launch("fp_threshold", k_fp_threshold, hgrid, block, st, A, S, HW);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
+// ---- the map ----------------------------------------------------------------------------------------------------------
+// The header's "Map build", a thread per destination pixel, fp64 in the stated order and without contraction: the
+// NumPy mirror (frame_prepare.remap_build_numpy) gives the same integers.
+__global__ __launch_bounds__(kFpThreads) void k_fp_remap_build(const mgs_remap_build_args B) {
+#pragma clang fp contract(off)
+  const int64_t i = (int64_t)blockIdx.x * kFpThreads + threadIdx.x;
+  if (i >= (int64_t)B.width * B.height) return;
+  const int vi = (int)(i / B.width), ui = (int)(i - (int64_t)vi * B.width);
+  const double u = (double)ui, v = (double)vi;
+  const double X = (B.ir[0] * u + B.ir[1] * v) + B.ir[2];
+  const double Y = (B.ir[3] * u + B.ir[4] * v) + B.ir[5];
+  const double Wd = (B.ir[6] * u + B.ir[7] * v) + B.ir[8];
+  const double x = X / Wd, y = Y / Wd;
+  const double x2 = x * x, y2 = y * y, r2 = x2 + y2, txy = (2.0 * x) * y;
+  const double k1 = B.dist[0], k2 = B.dist[1], p1 = B.dist[2], p2 = B.dist[3], k3 = B.dist[4];
+  const double kr = 1.0 + ((k3 * r2 + k2) * r2 + k1) * r2;
+  const double xd = (x * kr + p1 * txy) + p2 * (r2 + 2.0 * x2);
+  const double yd = (y * kr + p1 * (r2 + 2.0 * y2)) + p2 * txy;
+  const float mx = (float)(B.fx * xd + B.cx), my = (float)(B.fy * yd + B.cy);
+  int ix = -kFpMapClamp, iy = -kFpMapClamp;
+  if (isfinite(mx) && isfinite(my)) {
+    const double lim = (double)kFpMapClamp;
+    ix = (int)fmin(fmax(rint((double)mx * 32.0), -lim), lim);
+    iy = (int)fmin(fmax(rint((double)my * 32.0), -lim), lim);
+  }
+  reinterpret_cast<int2*>(B.map_q5)[i] = make_int2(ix, iy);
 }
 
 }  // namespace
@@ -336,7 +463,28 @@ uint64_t mgs_frame_prepare_scratch_bytes(int32_t H, int32_t W) {
 int32_t mgs_frame_prepare(const mgs_frame_prepare_args* args, void* stream) {
   const int32_t rc = mgs::frame_prepare_args_status(args);
   if (rc != MGS_OK) return rc;
-  return mgs::launch_frame_prepare(*args, (hipStream_t)stream);
+  return mgs::launch_frame_prepare(mgs::FpArgs<false>{*args}, (hipStream_t)stream);
+}
+
+int32_t mgs_remap_build_args_size(void) { return (int32_t)sizeof(mgs_remap_build_args); }
+int32_t mgs_frame_remap_args_size(void) { return (int32_t)sizeof(mgs_frame_remap_args); }
+
+int32_t mgs_remap_build(const mgs_remap_build_args* args, void* stream) {
+  if (!args || args->width < 1 || args->height < 1) return MGS_ERR_BAD_ARGUMENT;
+  if (!args->map_q5 || (reinterpret_cast<uintptr_t>(args->map_q5) & 7u)) return MGS_ERR_BAD_ARGUMENT;
+  const int64_t HW = (int64_t)args->width * args->height;
+  if (HW > 0x7fffffff) return MGS_ERR_UNSUPPORTED;
+  mgs::launch("fp_remap_build", mgs::k_fp_remap_build, dim3((unsigned)((HW + mgs::kFpThreads - 1) / mgs::kFpThreads)),
+              dim3(mgs::kFpThreads), (hipStream_t)stream, *args);
+  return mgs::launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
+int32_t mgs_frame_prepare_remapped(const mgs_frame_prepare_args* args, const mgs_frame_remap_args* remap, void* stream) {
+  int32_t rc = mgs::frame_prepare_args_status(args);
+  if (rc != MGS_OK) return rc;
+  rc = mgs::frame_remap_args_status(args, remap);
+  if (rc != MGS_OK) return rc;
+  return mgs::launch_frame_prepare(mgs::FpArgs<true>{*args, *remap}, (hipStream_t)stream);
 }
 
 }  // extern "C"

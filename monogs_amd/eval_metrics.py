@@ -168,10 +168,18 @@ class TUMSequence:
     """utils/dataset.py:50-124 (TUMParser): rgb / depth / ground-truth association within
     0.08 s, sub-sampled to at most 32 frames per second; `poses[i]` is the world-to-camera
     matrix inv(T_wc) of frame i.  Images are decoded with PIL on access (`image(i)` ->
-    float [3,H,W] in [0,1], `depth(i)` -> float [H,W] metres at `depth_scale`)."""
+    float [3,H,W] in [0,1], `depth(i)` -> float [H,W] metres at `depth_scale`).
 
-    def __init__(self, folder: str, frame_rate: float = 32, max_dt: float = 0.08, depth_scale: float = 5000.0):
+    `calibration`: a MonoGS Dataset.Calibration dict.  With `distorted` true, `image(i)` and `__getitem__` return the
+    frame undistorted on the host as MonocularDataset does it (utils/dataset.py:264-265), through the mirror of the
+    device's remap (frame_prepare.remap_build_numpy / remap_torch on the uint8 image), so that every consumer sees a
+    pinhole image; the depth is left as it is, as in the reference.  `image_u8(i)` is always the RAW uint8 [H,W,3]
+    image - what a FramePreparer built with the same calibration takes."""
+
+    def __init__(self, folder: str, frame_rate: float = 32, max_dt: float = 0.08, depth_scale: float = 5000.0,
+                 calibration=None):
         self.folder, self.depth_scale = folder, depth_scale
+        self.calibration, self._map = calibration, None
         pose_file = "groundtruth.txt" if os.path.isfile(os.path.join(folder, "groundtruth.txt")) else "pose.txt"
         rgb = _read_list(os.path.join(folder, "rgb.txt"))
         dep = _read_list(os.path.join(folder, "depth.txt"))
@@ -204,9 +212,19 @@ class TUMSequence:
     def __len__(self):
         return len(self.color_paths)
 
-    def image(self, i: int) -> torch.Tensor:
+    def image_u8(self, i: int) -> torch.Tensor:
         from PIL import Image
-        a = np.asarray(Image.open(self.color_paths[i]).convert("RGB"), dtype=np.float32) / 255.0
+        return torch.from_numpy(np.array(Image.open(self.color_paths[i]).convert("RGB"), dtype=np.uint8))
+
+    def image(self, i: int) -> torch.Tensor:
+        u8 = self.image_u8(i)
+        from .frame_prepare import calibration_remap, remap_build_numpy, remap_torch
+        cal = calibration_remap(self.calibration)
+        if cal is not None:
+            if self._map is None or tuple(self._map.shape[:2]) != tuple(u8.shape[:2]):
+                self._map = torch.from_numpy(remap_build_numpy(u8.shape[0], u8.shape[1], *cal)[1])
+            u8 = remap_torch(u8, self._map)
+        a = u8.numpy().astype(np.float32) / 255.0
         return torch.from_numpy(a).permute(2, 0, 1).contiguous()
 
     def depth(self, i: int) -> torch.Tensor:

@@ -41,10 +41,12 @@ from .tracking_native import NativeTracker
 
 
 class Frame:
-    """One input frame: image [3,H,W], optional sensor depth [H,W], ground-truth pose."""
+    """One input frame: image [3,H,W] (or, for a run that undistorts natively, the raw uint8 [H,W,3]), optional sensor
+    depth [H,W], ground-truth pose.  `undistorted`: the reader already remapped the image with a distorted calibration
+    (run_sequence refuses to remap such a frame a second time)."""
 
-    def __init__(self, uid, image, depth, T_gt):
-        self.uid, self.image, self.depth, self.T_gt = uid, image, depth, T_gt
+    def __init__(self, uid, image, depth, T_gt, undistorted: bool = False):
+        self.uid, self.image, self.depth, self.T_gt, self.undistorted = uid, image, depth, T_gt, undistorted
 
 
 def make_world(n_gaussians: int, W: int, H: int, poses: List[torch.Tensor], seed: int = 0, sigma_px: float = 2.5):
@@ -71,18 +73,27 @@ def trajectory(n_frames: int, step=(0.012, -0.006, 0.008, 0.004, -0.003, 0.002))
 
 
 def load_sequence(n_frames: int, W: int = 640, H: int = 480, dev="cuda", world_gaussians: int = 150_000, seed: int = 0,
-                  sigma_px: float = 2.5):
+                  sigma_px: float = 2.5, calibration: Optional[dict] = None, raw: bool = False):
     """(frames, camera, source): the mounted TUM sequence if MONOGS_TUM_DIR is set, else frames
-    rendered from a synthetic world along `trajectory`."""
-    cam = S.make_camera(W, H)
+    rendered from a synthetic world along `trajectory`.  `calibration`: a MonoGS Dataset.Calibration dict; the camera
+    is built from its fx, fy, cx, cy.  A mounted sequence with a `distorted` calibration is, by default, undistorted on
+    the host (TUMSequence(calibration=...)): the frames are pinhole images, marked `undistorted`, for a run_sequence
+    WITHOUT the calibration in its config.  `raw=True` hands the frames over as they are on disk (float [3,H,W], still
+    distorted) with the same camera: the input of run_sequence(native_frame_prepare=True, config=<with that
+    Dataset.Calibration>), which undistorts them on the device.  Synthetic frames are rendered with the pinhole camera
+    and are never marked: no distorted image exists to read."""
+    cam = S.make_camera(W, H, intrinsics=None if calibration is None else tuple(
+        float(calibration[k]) for k in ("fx", "fy", "cx", "cy")))
     tum = os.environ.get("MONOGS_TUM_DIR")
     if tum and os.path.isdir(tum):
         from .eval_metrics import TUMSequence
-        seq = TUMSequence(tum)
+        from .frame_prepare import calibration_remap
+        seq = TUMSequence(tum, calibration=None if raw else calibration)
+        done = not raw and calibration_remap(calibration) is not None
         frames = []
         for k in range(min(n_frames, len(seq))):
             img, depth, T = seq[k]
-            frames.append(Frame(k, img.to(dev), None if depth is None else depth.to(dev), T))
+            frames.append(Frame(k, img.to(dev), None if depth is None else depth.to(dev), T, undistorted=done))
         return frames, cam, f"TUM sequence at {tum}"
     from .gaussian_renderer import render
     poses = trajectory(n_frames)
@@ -160,7 +171,14 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     reference's per-frame compute_grad_mask) when its camera is made, inside the timed tracking section (frame 0:
     initialisation): the camera's grad_mask, rgb_pixel_mask, rgb_pixel_mask_mapping (and gt_depth with `sensor_depth`)
     are the preparer's, with Training.edge_threshold / rgb_boundary_threshold and Dataset.type from `config`; the
-    result then also holds `t_prepare`, the host time spent enqueuing those calls.  `track_on_edges` (needs
+    result then also holds `t_prepare`, the host time spent enqueuing those calls.  The preparer is built from `config`,
+    so a Dataset.Calibration with `distorted: True` there turns the undistortion on (mgs_frame_prepare_remapped, the map
+    built once on the device): the frames must then be RAW, distorted images - load_sequence(calibration=..., raw=True)'s
+    float [3,H,W], or uint8 [H,W,3] (TUMSequence.image_u8) - and frames a reader already undistorted
+    (load_sequence(calibration=...) without raw) are refused.  Every camera's original_image is then the preparer's
+    undistorted image, and everything downstream of the camera - keyframe seeding (keyframe_depth's content mask, the
+    seeder's colours) and evaluate()'s PSNR - reads that image, never the raw frame.  The sensor depth is left as it
+    is, as the reference's dataset leaves it.  `track_on_edges` (needs
     native_frame_prepare): tracking takes rgb_pixel_mask, upstream MonoGS's high-gradient pixels, as its pixel mask."""
     if track_on_edges and not native_frame_prepare:
         raise ValueError("track_on_edges needs native_frame_prepare=True (the edge mask is the preparer's)")
@@ -191,22 +209,30 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     if native_frame_prepare:
         from .frame_prepare import FramePreparer
         preparer = FramePreparer(H, W, dev, cfg)
+        if preparer.map_q5 is not None and any(getattr(f, "undistorted", False) for f in frames):
+            raise ValueError("the frames were undistorted by their reader and config's Dataset.Calibration would remap "
+                             "them again: read them with load_sequence(..., raw=True) or drop the calibration")
+    if preparer is None and any(f.image.dtype == torch.uint8 for f in frames):
+        raise ValueError("uint8 frames need native_frame_prepare=True (the preparer converts them)")
 
     def insert(gm_, fr: Frame, view, k, init, depth=None, opacity=None):
-        """New Gaussians of keyframe k: add_new_keyframe's depth map, then create_pcd + extend_from_pcd."""
+        """New Gaussians of keyframe k: add_new_keyframe's depth map, then create_pcd + extend_from_pcd.  The image
+        is the camera's (the frame's own, or the preparer's undistorted one), never the raw frame."""
         if seeder is None:
-            dm = keyframe_depth(fr.image, depth, opacity, fr.depth if sensor_depth else None, gen)
+            dm = keyframe_depth(view.original_image, depth, opacity, fr.depth if sensor_depth else None, gen)
             gm_.extend_from_pcd_seq(view, kf_id=k, init=init, depthmap=dm, generator=gen)
             return
         if sensor_depth:
             mode, depth, opacity = MODE_SENSOR, fr.depth, None
         else:
             mode = MODE_INITIAL if depth is None else MODE_RENDERED
-        seed_records[k] = gm_.extend_from_keyframe(seeder, view, fr.image, depth, opacity, mode, init,
+        seed_records[k] = gm_.extend_from_keyframe(seeder, view, view.original_image, depth, opacity, mode, init,
                                                    seed * 1_000_003 + k, kf_id=k)
 
     def camera(fr: Frame, T):
-        v = ViewCamera(fr.uid, fr.image, T, cam.projmatrix_raw, fovx, fovy, H, W, dev,
+        # (a raw uint8 [H,W,3] frame: the camera starts empty and the preparer below converts the frame into it)
+        first = fr.image if fr.image.dtype != torch.uint8 else torch.zeros(3, H, W, device=dev)
+        v = ViewCamera(fr.uid, first, T, cam.projmatrix_raw, fovx, fovy, H, W, dev,
                        intrinsics=(cam.fx, cam.fy, cam.cx, cam.cy))
         v.T_gt = fr.T_gt
         if preparer is not None:
@@ -319,7 +345,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
 def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
     """ATE RMSE over all tracked frames and over the keyframes (Sim(3)-aligned when `monocular`:
     the scale of a monocular map is free; SE(3)-aligned otherwise, eval_utils.py:26-44),
-    PSNR of the final map rendered at the estimated poses of the non-keyframes."""
+    PSNR of the final map rendered at the estimated poses of the non-keyframes, against each camera's own
+    original_image (the frame's image; with a native remap the undistorted one, not the raw frame)."""
     from . import eval_metrics as E
     from .gaussian_renderer import render
     cams, gm = result["cameras"], result["gaussians"]
@@ -337,6 +364,6 @@ def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
             v = cams[i]
             img = render(v, gm, Pipe, bg)["render"]
             img = ((torch.abs(v.exposure_a) + v.exposure_eps) * img + v.exposure_b).clamp(0, 1)
-            ps.append(float(E.psnr(img.unsqueeze(0), frames[i].image.unsqueeze(0))))
+            ps.append(float(E.psnr(img.unsqueeze(0), v.original_image.unsqueeze(0))))
     return {"ate_rmse_m": ate_all, "ate_rmse_keyframes_m": ate_kf, "path_length_m": path,
             "psnr_db": sum(ps) / max(1, len(ps)), "psnr_frames": len(ps), "gaussians": len(gm)}

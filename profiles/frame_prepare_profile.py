@@ -1,23 +1,34 @@
 """Frame preparation on the GPU box, the torch mirror against the native call:
 
     timeout -k 10 300 python profiles/frame_prepare_profile.py > profiles/frame_prepare_profile.txt
-    for c in 0 1 2; do for p in native mirror; do
+    for c in 0 1 2 3 4; do for p in native mirror; do
       timeout -k 10 120 rocprofv3 --kernel-trace --stats --output-format csv -d <dir>/trace_${p}_$c -o run -- \
           python profiles/frame_prepare_profile.py --$p-only --config $c
     done; done
     python profiles/frame_prepare_profile.py --summarise <dir> >> profiles/frame_prepare_profile.txt
         (also writes <dir>/frame_prepare_kernel_stats.csv)
 
-Three configurations, inputs resident on the device in the format named:
+Five configurations, inputs resident on the device in the format named:
   0  640x480, global mode (Dataset.type tum, edge_threshold 1.1), uint8 [H,W,3] image
   1  640x480, global mode, float [3,H,W] image
   2  1200x680, patch mode (Dataset.type replica, edge_threshold 4), uint8 image and uint16 depth (depth_scale 6553.5)
+  3  configuration 0 undistorted: fr1_desk's calibration (Dataset.Calibration, distorted: True), the map built on the
+     device once, every call mgs_frame_prepare_remapped
+  4  configuration 2 undistorted: the same coefficients, the intrinsics scaled to 1200x680
+     (3 and 4 also time the un-remapped native call of the same build on the same input: the cost of the remap is the
+     difference; their mirror is prepare_frame_torch(remap=...))
   (a) frame_prepare.prepare_frame_torch on the device: wall clock per call with a final synchronise;
   (b) FramePreparer.prepare: one mgs_frame_prepare call; same protocol.
 Each figure is the median of 50 calls after 10 warm-ups, the two paths alternating in blocks of 25, with the quartiles
 and extremes of the 50 (the spread).  Synchronising torch operators are counted with torch's sync debug mode.
 --native-only / --mirror-only run 20 calls of one configuration and nothing else, for a kernel trace: the trace's
-dispatch count over 20 is the launches per call; --summarise turns the traces into the per-kernel table."""
+dispatch count over 20 is the launches per call; --summarise turns the traces into the per-kernel table.
+
+The block that ends frame_prepare_profile.txt ("the un-remapped call against the parent commit's build ...") is not
+printed by a mode of this script.  Its procedure: check the parent commit out into a directory of its own and build it
+there; on ONE box run `python profiles/frame_prepare_profile.py` from the parent's directory and from this one
+alternately, twice each; copy the `native` median and quartiles of configurations 0 / 1 / 2 from each output (and, from
+this build's outputs, the rows of configurations 3 and 4) into that block by hand."""
 import csv
 import glob
 import json
@@ -33,7 +44,13 @@ CONFIGS = (
     {"name": "640x480 global float", "H": 480, "W": 640, "type": "tum", "edge_threshold": 1.1, "u8": False, "depth": False},
     {"name": "1200x680 patch uint8 + uint16 depth", "H": 680, "W": 1200, "type": "replica", "edge_threshold": 4.0,
      "u8": True, "depth": True},
+    {"name": "640x480 global uint8, remapped (fr1_desk)", "H": 480, "W": 640, "type": "tum", "edge_threshold": 1.1,
+     "u8": True, "depth": False, "remap": True},
+    {"name": "1200x680 patch uint8 + uint16 depth, remapped (fr1_desk scaled)", "H": 680, "W": 1200, "type": "replica",
+     "edge_threshold": 4.0, "u8": True, "depth": True, "remap": True},
 )
+FR1_DESK = {"fx": 517.3, "fy": 516.5, "cx": 318.6, "cy": 255.3, "k1": 0.2624, "k2": -0.9531, "p1": -0.0054,
+            "p2": 0.0026, "k3": 1.1633, "width": 640, "height": 480, "distorted": True}
 DEPTH_SCALE = 6553.5
 
 
@@ -99,17 +116,26 @@ def paths(cfg, dev):
     from monogs_amd import frame_prepare as FP
     image, depth = inputs(cfg, dev)
     scale = DEPTH_SCALE if cfg["depth"] else None
-    P = FP.FramePreparer(cfg["H"], cfg["W"], dev, {"Training": {"edge_threshold": cfg["edge_threshold"]},
-                                                   "Dataset": {"type": cfg["type"]}})
+    config = {"Training": {"edge_threshold": cfg["edge_threshold"]}, "Dataset": {"type": cfg["type"]}}
+    plain = FP.FramePreparer(cfg["H"], cfg["W"], dev, config)
+    P = plain
+    if cfg.get("remap"):
+        sx, sy = cfg["W"] / 640.0, cfg["H"] / 480.0
+        cal = dict(FR1_DESK, fx=FR1_DESK["fx"] * sx, fy=FR1_DESK["fy"] * sy, cx=FR1_DESK["cx"] * sx,
+                   cy=FR1_DESK["cy"] * sy, width=cfg["W"], height=cfg["H"])
+        P = FP.FramePreparer(cfg["H"], cfg["W"], dev, config, calibration=cal)
 
     def mirror():
         return FP.prepare_frame_torch(image, depth, dataset_type=cfg["type"], edge_threshold=cfg["edge_threshold"],
-                                      depth_scale=scale)
+                                      depth_scale=scale, remap=P.map_q5)
 
     def native():
         return P.prepare(image, depth, scale)
 
-    return mirror, native
+    def unremapped():
+        return plain.prepare(image, depth, scale)
+
+    return mirror, native, unremapped
 
 
 def measure():
@@ -117,7 +143,7 @@ def measure():
     dev = torch.device("cuda:0")
     out = []
     for cfg in CONFIGS:
-        mirror, native = paths(cfg, dev)
+        mirror, native, unremapped = paths(cfg, dev)
         a, b = mirror(), native()
         torch.cuda.synchronize()
         row = {"config": cfg["name"], "H": cfg["H"], "W": cfg["W"],
@@ -125,8 +151,12 @@ def measure():
                "edge_mask_cover": round(float(b["grad_mask"].mean()), 4)}
         # alternate the two paths so that a drift of the host hits both
         a1, b1 = samples_us(mirror, 10, 25), samples_us(native, 10, 25)
+        c1 = samples_us(unremapped, 10, 25) if cfg.get("remap") else None
         a2, b2 = samples_us(mirror, 0, 25), samples_us(native, 0, 25)
         row["torch_mirror"], row["native"] = summary(a1 + a2), summary(b1 + b2)
+        if c1 is not None:
+            row["image_bits_equal_mirror"] = bool(torch.equal(a["image"], b["image"]))
+            row["native_unremapped"] = summary(c1 + samples_us(unremapped, 0, 25))
         row["torch_mirror_host_syncs"], row["native_host_syncs"] = count_syncs(mirror), count_syncs(native)
         a, b = row["torch_mirror"], row["native"]
         row["speedup_median"] = round(a["median_us"] / b["median_us"], 2)
@@ -137,13 +167,19 @@ def measure():
               f"{b['median_us']} us (quartiles {b['q1_us']} .. {b['q3_us']}, range {b['min_us']} .. {b['max_us']}; "
               f"{row['native_host_syncs']} synchronising operators), x{row['speedup_median']}; edge mask covers "
               f"{100 * row['edge_mask_cover']:.1f} %, {row['mask_pixels_differing']} mask pixels differ")
+        if "native_unremapped" in row:
+            c = row["native_unremapped"]
+            row["remap_cost_us"] = round(b["median_us"] - c["median_us"], 1)
+            print(f"    the un-remapped native call of this build on the same input: {c['median_us']} us (quartiles "
+                  f"{c['q1_us']} .. {c['q3_us']}, range {c['min_us']} .. {c['max_us']}): the remap costs "
+                  f"{row['remap_cost_us']} us; image bit-equal to the mirror's: {row['image_bits_equal_mirror']}")
         out.append(row)
     print(json.dumps({"frame_prepare_profile": out}))
 
 
 def traced(which, index):
     import torch
-    mirror, native = paths(CONFIGS[index], torch.device("cuda:0"))
+    mirror, native, _ = paths(CONFIGS[index], torch.device("cuda:0"))
     fn = native if which == "native" else mirror
     for _ in range(CALLS_TRACED):
         fn()
