@@ -904,6 +904,73 @@ int32_t mgs_remap_build(const mgs_remap_build_args* args, void* stream);
  * Checked before anything is launched or written. */
 int32_t mgs_frame_prepare_remapped(const mgs_frame_prepare_args* args, const mgs_frame_remap_args* remap, void* stream);
 
+/* ---- stereo depth (stereo_depth.hip; DESIGN.md "Stereo depth on the device") ---------------------------------------
+ * What the reference's StereoDataset.__getitem__ does to every frame on the host (utils/dataset.py:367-395): rectify
+ * both images, cv2.StereoSGBM_create(minDisparity=0, numDisparities=64, blockSize=20) with setUniquenessRatio(40),
+ * depth = bf / disparity.  The algorithm restates OpenCV's single-pass MODE_SGBM from knowledge of it; parity with cv2
+ * is UNPINNED (no cv2 to produce a fixture with).  The contract is this library's own: every step is integer arithmetic
+ * and kernels and mirror (stereo_depth.stereo_sgbm_numpy) agree bit for bit.
+ *
+ * Grey.  The rectified grey uint8 images L, R [H][W] come from the inputs by image_format:
+ *   U8_GREY  the byte itself;  U8_HWC (RGB order)  (4899*r + 9617*g + 1868*b + 8192) >> 14 (OpenCV's fixed point);
+ *   F32_CHW  each channel to k = clamp(rint_half_even(v * 255 in fp32), 0, 255) (NaN: 0), then as U8_HWC.
+ * With a map (map_left / map_right, the int32 [H][W][2] 1/32-pixel maps of mgs_remap_build) every channel is first
+ * gathered exactly as "Remap" above states it (uint8: the rounded integer blend, a byte again; float: the fp32 blend),
+ * with a constant 0 border, and then reduced to grey.  image (optional) = float32(L / 255.0) in all three channels.
+ *
+ * Constants: D = 64 disparities d = 0..63, minDisparity 0; half block r = block_size / 2 (21 x 21 at 20); P1 = 2,
+ * P2 = 5; ftzero = 15; disp12MaxDiff = 0; valid columns x in [D, W).
+ *   prefilter   g = clip(2*(I[y,x+1]-I[y,x-1]) + (I[y-1,x+1]-I[y-1,x-1]) + (I[y+1,x+1]-I[y+1,x-1]), -15, 15) + 15, rows
+ *               clamped at the border, g = 15 in the first and the last column.
+ *   pixel cost  Birchfield-Tomasi on the two channels g and I.  For u at x (neighbours clamped): ul = (u + u[x-1]) / 2,
+ *               ur = (u + u[x+1]) / 2, u0 = min(u, ul, ur), u1 = max(u, ul, ur); the same for v = R[x-d];
+ *               c = min(max(0, u - v1, v0 - u), max(0, v - u1, u0 - v)) >> 2; the cost is c(g) + c(I), at most 70.
+ *   block cost  C(x,y,d) = the pixel cost summed over |dx| <= r, |dy| <= r with y clamped to [0, H-1] and x to [D, W-1].
+ *   paths       five, the predecessor q of p = (x,y) being (x-1,y), (x+1,y), (x-1,y-1), (x,y-1), (x+1,y-1):
+ *               L(p,d) = C(p,d) + min(L(q,d), L(q,d-1) + P1, L(q,d+1) + P1, m_q + P2) - m_q, m_q = min_d L(q,d), d-1 / d+1
+ *               outside 0..63 left out; q outside the valid region: L(p,.) = C(p,.).  S = the sum of the five.
+ *   selection   b = argmin_d S (the smallest d on ties).  Not unique - invalid - if some d with |d - b| > 1 has
+ *               S[d] * (100 - uniqueness_ratio) < S[b] * 100.  0 < b < 63: den = max(S[b-1] + S[b+1] - 2*S[b], 1),
+ *               disp16 = 16*b + ((S[b-1] - S[b+1]) * 16 + den) / (2*den) (C division); else disp16 = 16*b.  Invalid pixels
+ *               and all of x < D hold -16.
+ *   left-right  every unique pixel votes (S[b], b) into x2 = x - b; a column keeps the smallest S, on ties the smallest
+ *               b.  A valid pixel with d1 = disp16 is invalidated if both candidates d1 >> 4 and (d1 + 15) >> 4
+ *               disagree: a candidate c disagrees when x - c is inside the row, holds a vote, and that vote's b != c.
+ *   depth       disp = disp16 / 16.0 (double); disp == 0 -> 1e10; depth = float32(bf / disp); depth < 0 -> 0.
+ * Two calls with the same inputs give identical bits (integer sums only). */
+#define MGS_STEREO_IMAGE_U8_GREY 0
+#define MGS_STEREO_IMAGE_U8_HWC 1
+#define MGS_STEREO_IMAGE_F32_CHW 2
+#define MGS_STEREO_DISPARITIES 64
+
+typedef struct mgs_stereo_depth_args {
+  int32_t width, height;           /* width > 64 */
+  int32_t image_format;            /* MGS_STEREO_IMAGE_*, of both inputs */
+  int32_t num_disparities;         /* 64 (anything else: MGS_ERR_UNSUPPORTED) */
+  int32_t block_size;              /* the reference's 20; half block block_size / 2 <= 14 */
+  int32_t uniqueness_ratio;        /* 0..100; the reference's 40 */
+  double bf;                       /* baseline * fx; the reference's 47.90639384423901 */
+  const void* left_in;             /* uint8 [H][W], uint8 [H][W][3] or float [3][H][W] */
+  const void* right_in;
+  const int32_t* map_left;         /* device int32 [H][W][2], 8-byte aligned, or NULL: the input is rectified already */
+  const int32_t* map_right;
+  float* depth;                    /* [H][W] */
+  int16_t* disp16;                 /* [H][W], or NULL */
+  float* image;                    /* [3][H][W] the rectified left grey / 255, or NULL */
+  void* scratch;                   /* mgs_stereo_scratch_bytes(H, W) bytes, 16-byte aligned; nothing is asked of the
+                                      caller */
+} mgs_stereo_depth_args;
+
+/* sizeof(mgs_stereo_depth_args), for a binding to verify its mirror (as mgs_frame_prepare_args_size). */
+int32_t mgs_stereo_depth_args_size(void);
+/* 0 for sizes the call refuses (W <= 64, a side beyond 16 384). */
+uint64_t mgs_stereo_scratch_bytes(int32_t H, int32_t W);
+/* Every argument is checked before anything is launched or written: a null struct, input, depth or scratch, W <= 64,
+ * an unknown format, block_size < 1, a uniqueness_ratio outside 0..100, a misaligned scratch or map give
+ * MGS_ERR_BAD_ARGUMENT; num_disparities != 64, block_size / 2 > 14 or a side beyond 16 384 MGS_ERR_UNSUPPORTED.
+ * Seven launches and one memset node on `stream`.  No host read, no synchronisation. */
+int32_t mgs_stereo_depth(const mgs_stereo_depth_args* args, void* stream);
+
 /* ---- map maintenance on the device ---------------------------------- */
 
 #define MGS_ADAM_MAX_GROUPS 8

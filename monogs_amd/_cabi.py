@@ -32,6 +32,7 @@ EXPORTS = (
     "mgs_keyframe_scratch_bytes", "mgs_keyframe_decide", "mgs_keyframe_seed_scratch_bytes", "mgs_keyframe_seed",
     "mgs_frame_prepare_args_size", "mgs_frame_prepare_scratch_bytes", "mgs_frame_prepare",
     "mgs_remap_build_args_size", "mgs_frame_remap_args_size", "mgs_remap_build", "mgs_frame_prepare_remapped",
+    "mgs_stereo_depth_args_size", "mgs_stereo_scratch_bytes", "mgs_stereo_depth",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -281,6 +282,18 @@ class FrameRemapArgs(C.Structure):
     _fields_ = [("map_q5", _fp), ("depth_mode", C.c_int32), ("reserved0", C.c_int32)]
 
 
+STEREO_IMAGE_U8_GREY, STEREO_IMAGE_U8_HWC, STEREO_IMAGE_F32_CHW = 0, 1, 2
+STEREO_DISPARITIES = 64
+
+
+class StereoDepthArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "image_format", "num_disparities", "block_size",
+                                          "uniqueness_ratio")]
+                + [("bf", C.c_double)]
+                + [(n, _fp) for n in ("left_in", "right_in", "map_left", "map_right", "depth", "disp16", "image",
+                                      "scratch")])
+
+
 _lib = None
 
 
@@ -424,6 +437,13 @@ def lib():
     L.mgs_remap_build.argtypes = [C.POINTER(RemapBuildArgs), C.c_void_p]
     L.mgs_frame_prepare_remapped.restype = C.c_int32
     L.mgs_frame_prepare_remapped.argtypes = [C.POINTER(FramePrepareArgs), C.POINTER(FrameRemapArgs), C.c_void_p]
+    L.mgs_stereo_depth_args_size.restype, L.mgs_stereo_depth_args_size.argtypes = C.c_int32, []
+    if L.mgs_stereo_depth_args_size() != C.sizeof(StereoDepthArgs):
+        raise NativeLibraryError("StereoDepthArgs does not have the size of mgs_stereo_depth_args")
+    L.mgs_stereo_scratch_bytes.restype = C.c_uint64
+    L.mgs_stereo_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.mgs_stereo_depth.restype = C.c_int32
+    L.mgs_stereo_depth.argtypes = [C.POINTER(StereoDepthArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

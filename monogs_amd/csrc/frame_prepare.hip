@@ -28,6 +28,7 @@
 #include "launch.h"
 #include "radix_select.h"
 #include "raster_kernels.h"
+#include "remap_gather.h"
 #include "rn_math.h"
 
 namespace mgs {
@@ -76,46 +77,9 @@ struct FpArgs<true> { mgs_frame_prepare_args a; mgs_frame_remap_args r; };
 
 constexpr int kFpMapClamp = 1 << 30;   // |ix|, |iy| <= 2^30: ix + 32 and ix + 16 stay inside int32
 
-// One destination pixel's four taps (header: "Remap"): offsets into an [H][W] plane, -1 for a tap outside the image -
-// the bounds are checked before an address is formed - and the integer weights.
-struct FpTaps {
-  int2 q;                                                          // the map entry (ix, iy) itself
-  int64_t o00, o01, o10, o11;
-  int w00, w01, w10, w11;
-};
-
-__device__ __forceinline__ FpTaps remap_taps(const int32_t* map_q5, size_t p, int H, int W) {
-  const int2 q = reinterpret_cast<const int2*>(map_q5)[p];        // (ix, iy): one 8-byte load
-  const int sx = q.x >> 5, sy = q.y >> 5, ax = q.x & 31, ay = q.y & 31;
-  const bool x0 = sx >= 0 && sx < W, x1 = sx >= -1 && sx < W - 1;
-  const bool y0 = sy >= 0 && sy < H, y1 = sy >= -1 && sy < H - 1;
-  FpTaps t;
-  t.q = q;
-  t.o00 = y0 && x0 ? (int64_t)sy * W + sx : -1;
-  t.o01 = y0 && x1 ? (int64_t)sy * W + (sx + 1) : -1;
-  t.o10 = y1 && x0 ? (int64_t)(sy + 1) * W + sx : -1;
-  t.o11 = y1 && x1 ? (int64_t)(sy + 1) * W + (sx + 1) : -1;
-  t.w00 = (32 - ax) * (32 - ay);
-  t.w01 = ax * (32 - ay);
-  t.w10 = (32 - ax) * ay;
-  t.w11 = ax * ay;
-  return t;
-}
-
-__device__ __forceinline__ int tap_u8(const uint8_t* u, int64_t o, int c) { return o >= 0 ? (int)u[3 * o + c] : 0; }
-__device__ __forceinline__ float tap_f32(const float* f, int64_t o) { return o >= 0 ? f[o] : 0.f; }
-
+// (the taps and blends of the remap themselves: remap_gather.h)
 __device__ __forceinline__ float blend_u8(const FpTaps& t, const uint8_t* u, int c, const float* s_lut) {
-  const int k = (t.w00 * tap_u8(u, t.o00, c) + t.w01 * tap_u8(u, t.o01, c) + t.w10 * tap_u8(u, t.o10, c) +
-                 t.w11 * tap_u8(u, t.o11, c) + 512) >> 10;
-  return s_lut[k];
-}
-
-__device__ __forceinline__ float blend_f32(const FpTaps& t, const float* f) {
-#pragma clang fp contract(off)
-  const float f00 = (float)t.w00 * 0.0009765625f, f01 = (float)t.w01 * 0.0009765625f;     // w / 1024: exact
-  const float f10 = (float)t.w10 * 0.0009765625f, f11 = (float)t.w11 * 0.0009765625f;
-  return (f00 * tap_f32(f, t.o00) + f01 * tap_f32(f, t.o01)) + (f10 * tap_f32(f, t.o10) + f11 * tap_f32(f, t.o11));
+  return s_lut[blend_u8_int(t, u, c)];
 }
 
 __device__ __forceinline__ float convert_depth(const mgs_frame_prepare_args& A, size_t p) {

@@ -27,6 +27,7 @@ from __future__ import annotations
 import math
 import os
 import time
+from types import SimpleNamespace
 from typing import List, Optional
 
 import torch
@@ -43,10 +44,12 @@ from .tracking_native import NativeTracker
 class Frame:
     """One input frame: image [3,H,W] (or, for a run that undistorts natively, the raw uint8 [H,W,3]), optional sensor
     depth [H,W], ground-truth pose.  `undistorted`: the reader already remapped the image with a distorted calibration
-    (run_sequence refuses to remap such a frame a second time)."""
+    (run_sequence refuses to remap such a frame a second time).  `image_right`: the right image of a stereo pair, in
+    the left image's format (run_sequence(stereo_matcher=...) makes the frame's depth from the two)."""
 
-    def __init__(self, uid, image, depth, T_gt, undistorted: bool = False):
+    def __init__(self, uid, image, depth, T_gt, undistorted: bool = False, image_right=None):
         self.uid, self.image, self.depth, self.T_gt, self.undistorted = uid, image, depth, T_gt, undistorted
+        self.image_right = image_right
 
 
 def make_world(n_gaussians: int, W: int, H: int, poses: List[torch.Tensor], seed: int = 0, sigma_px: float = 2.5):
@@ -73,7 +76,8 @@ def trajectory(n_frames: int, step=(0.012, -0.006, 0.008, 0.004, -0.003, 0.002))
 
 
 def load_sequence(n_frames: int, W: int = 640, H: int = 480, dev="cuda", world_gaussians: int = 150_000, seed: int = 0,
-                  sigma_px: float = 2.5, calibration: Optional[dict] = None, raw: bool = False):
+                  sigma_px: float = 2.5, calibration: Optional[dict] = None, raw: bool = False,
+                  stereo_baseline: Optional[float] = None):
     """(frames, camera, source): the mounted TUM sequence if MONOGS_TUM_DIR is set, else frames
     rendered from a synthetic world along `trajectory`.  `calibration`: a MonoGS Dataset.Calibration dict; the camera
     is built from its fx, fy, cx, cy.  A mounted sequence with a `distorted` calibration is, by default, undistorted on
@@ -81,11 +85,16 @@ def load_sequence(n_frames: int, W: int = 640, H: int = 480, dev="cuda", world_g
     WITHOUT the calibration in its config.  `raw=True` hands the frames over as they are on disk (float [3,H,W], still
     distorted) with the same camera: the input of run_sequence(native_frame_prepare=True, config=<with that
     Dataset.Calibration>), which undistorts them on the device.  Synthetic frames are rendered with the pinhole camera
-    and are never marked: no distorted image exists to read."""
+    and are never marked: no distorted image exists to read.  `stereo_baseline` (synthetic frames only): every frame
+    also gets `image_right`, the view of a second camera shifted by the baseline along the left camera's +x, and both
+    views are quantised to grey uint8 [H,W] (stereo_depth.to_grey_numpy's rule for a float image) - a rectified pair
+    whose disparity is fx * baseline / depth; `depth` stays the left view's rendered depth."""
     cam = S.make_camera(W, H, intrinsics=None if calibration is None else tuple(
         float(calibration[k]) for k in ("fx", "fy", "cx", "cy")))
     tum = os.environ.get("MONOGS_TUM_DIR")
     if tum and os.path.isdir(tum):
+        if stereo_baseline is not None:
+            raise ValueError("stereo_baseline renders a second view of the synthetic world; a mounted sequence has none")
         from .eval_metrics import TUMSequence
         from .frame_prepare import calibration_remap
         seq = TUMSequence(tum, calibration=None if raw else calibration)
@@ -103,11 +112,24 @@ def load_sequence(n_frames: int, W: int = 640, H: int = 480, dev="cuda", world_g
     fovx, fovy = 2 * math.atan(cam.tanfovx), 2 * math.atan(cam.tanfovy)
     bg = torch.zeros(3, device=dev)
     frames = []
+
+    def grey_u8(img):
+        k = (img.to(torch.float32) * 255.0).round().clamp(0, 255).to(torch.int64)
+        return ((4899 * k[0] + 9617 * k[1] + 1868 * k[2] + 8192) >> 14).to(torch.uint8)
+
     with torch.no_grad():
         for k, T in enumerate(poses):
             v = ViewCamera(k, torch.zeros(3, H, W), T, cam.projmatrix_raw, fovx, fovy, H, W, dev)
             pkg = render(v, world, Pipe, bg)
-            frames.append(Frame(k, pkg["render"].clamp(0, 1).clone(), pkg["depth"][0].clone(), T))
+            image, depth = pkg["render"].clamp(0, 1).clone(), pkg["depth"][0].clone()
+            if stereo_baseline is None:
+                frames.append(Frame(k, image, depth, T))
+                continue
+            Tr = T.clone()
+            Tr[0, 3] -= float(stereo_baseline)                    # the right camera's centre: +baseline along the left's x
+            vr = ViewCamera(k, torch.zeros(3, H, W), Tr, cam.projmatrix_raw, fovx, fovy, H, W, dev)
+            right = render(vr, world, Pipe, bg)["render"].clamp(0, 1)
+            frames.append(Frame(k, grey_u8(image), depth, T, image_right=grey_u8(right)))
     return frames, cam, f"synthetic world, {world_gaussians} Gaussians, {n_frames} frames @ {W}x{H}"
 
 
@@ -152,7 +174,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  second_order_iters: int = 10, seed: int = 0, config: Optional[dict] = None, log=None,
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
-                 native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False):
+                 native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
+                 stereo_matcher=None):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -179,10 +202,18 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     undistorted image, and everything downstream of the camera - keyframe seeding (keyframe_depth's content mask, the
     seeder's colours) and evaluate()'s PSNR - reads that image, never the raw frame.  The sensor depth is left as it
     is, as the reference's dataset leaves it.  `track_on_edges` (needs
-    native_frame_prepare): tracking takes rgb_pixel_mask, upstream MonoGS's high-gradient pixels, as its pixel mask."""
+    native_frame_prepare): tracking takes rgb_pixel_mask, upstream MonoGS's high-gradient pixels, as its pixel mask.
+    `stereo_matcher`: a stereo_depth.StereoMatcher; every frame then carries a pair (`image`, `image_right`), its depth
+    is the matcher's (one mgs_stereo_depth call when its camera is made), the
+    camera's image is the matcher's rectified left image, and from there the run is `sensor_depth=True`'s with that
+    depth in the place of `frame.depth` - what the reference's stereo dataset hands its frontend."""
+    if stereo_matcher is not None:
+        if any(getattr(f, "image_right", None) is None for f in frames):
+            raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
+        sensor_depth = True
     if track_on_edges and not native_frame_prepare:
         raise ValueError("track_on_edges needs native_frame_prepare=True (the edge mask is the preparer's)")
-    if rgbd_tracking and (not sensor_depth or any(f.depth is None for f in frames)):
+    if rgbd_tracking and (not sensor_depth or (stereo_matcher is None and any(f.depth is None for f in frames))):
         raise ValueError("rgbd_tracking needs sensor_depth=True and a depth image in every frame")
     policy = keyframe_policy
     if policy is not None:
@@ -212,18 +243,24 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         if preparer.map_q5 is not None and any(getattr(f, "undistorted", False) for f in frames):
             raise ValueError("the frames were undistorted by their reader and config's Dataset.Calibration would remap "
                              "them again: read them with load_sequence(..., raw=True) or drop the calibration")
-    if preparer is None and any(f.image.dtype == torch.uint8 for f in frames):
+    if preparer is None and stereo_matcher is None and any(f.image.dtype == torch.uint8 for f in frames):
         raise ValueError("uint8 frames need native_frame_prepare=True (the preparer converts them)")
+
+    stereo_depths = {}
+
+    def depth_of(fr: Frame):
+        """The frame's sensor depth [H,W]: its own, or the one the matcher made when its camera was."""
+        return stereo_depths[fr.uid][0] if stereo_matcher is not None else fr.depth
 
     def insert(gm_, fr: Frame, view, k, init, depth=None, opacity=None):
         """New Gaussians of keyframe k: add_new_keyframe's depth map, then create_pcd + extend_from_pcd.  The image
         is the camera's (the frame's own, or the preparer's undistorted one), never the raw frame."""
         if seeder is None:
-            dm = keyframe_depth(view.original_image, depth, opacity, fr.depth if sensor_depth else None, gen)
+            dm = keyframe_depth(view.original_image, depth, opacity, depth_of(fr) if sensor_depth else None, gen)
             gm_.extend_from_pcd_seq(view, kf_id=k, init=init, depthmap=dm, generator=gen)
             return
         if sensor_depth:
-            mode, depth, opacity = MODE_SENSOR, fr.depth, None
+            mode, depth, opacity = MODE_SENSOR, depth_of(fr), None
         else:
             mode = MODE_INITIAL if depth is None else MODE_RENDERED
         seed_records[k] = gm_.extend_from_keyframe(seeder, view, view.original_image, depth, opacity, mode, init,
@@ -231,14 +268,19 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
 
     def camera(fr: Frame, T):
         # (a raw uint8 [H,W,3] frame: the camera starts empty and the preparer below converts the frame into it)
-        first = fr.image if fr.image.dtype != torch.uint8 else torch.zeros(3, H, W, device=dev)
+        image = fr.image
+        if stereo_matcher is not None:                  # the pair becomes the camera's image and the frame's depth
+            rectified = SimpleNamespace()
+            stereo_depths[fr.uid] = stereo_matcher.compute_into(rectified, fr.image, fr.image_right)
+            image = rectified.original_image
+        first = image if image.dtype != torch.uint8 else torch.zeros(3, H, W, device=dev)
         v = ViewCamera(fr.uid, first, T, cam.projmatrix_raw, fovx, fovy, H, W, dev,
                        intrinsics=(cam.fx, cam.fy, cam.cx, cam.cy))
         v.T_gt = fr.T_gt
         if preparer is not None:
             nonlocal t_prepare
             tp = time.perf_counter()
-            preparer.prepare_into(v, fr.image, fr.depth if sensor_depth else None)
+            preparer.prepare_into(v, image, depth_of(fr) if sensor_depth else None)
             t_prepare += time.perf_counter() - tp
         return v
 
@@ -268,7 +310,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         t0 = time.perf_counter()
         if preparer is not None:                                  # the frame's preparation is part of its tracking time
             vp = camera(fr, cams[k - 1].T.detach().clone())
-        trk = NativeTracker(vp, gm, bg, gt_depth=fr.depth if rgbd_tracking else None, alpha=alpha,
+        trk = NativeTracker(vp, gm, bg, gt_depth=depth_of(fr) if rgbd_tracking else None, alpha=alpha,
                             num_pixels=num_pixels, sample_seed=seed + k,
                             mask=vp.rgb_pixel_mask if track_on_edges else None)
         if second_order_iters > 0:
