@@ -1226,6 +1226,40 @@ typedef struct mgs_refine_view_args {
 
 int32_t mgs_refine_view_iteration(const mgs_refine_view_args* args, void* stream);
 
+/* ---- dense Gauss-Newton tracking iteration ("Dense Gauss-Newton tracking") -----------------
+ * The second-order iteration WITHOUT the sketch: every pixel p is a row of its own,
+ *   f_p = s * sum_c Huber(r_pc),  s = stack_dim * sketch_dim / (H*W),  J_p = d f_p / d [rho; theta; a; b]
+ * (r_pc, the mask, the opacity, Huber, the depth row and ApplyExposure's hand-written backward exactly as in
+ * mgs_sketch_residual[_rgbd] with every weight +1), and the step solves (H + lambda I) x = -g with
+ *   H = sum_p J_p^T J_p,  g = sum_p J_p^T f_p   over ALL H*W pixels.
+ * stack_dim / sketch_dim only enter through s, which makes H the expectation of the sketched SJ^T SJ, so that the
+ * lm block (lambdas, factors, thresholds, lm_state, best) means what it means in mgs_tracking_iteration_second_order.
+ * Launch sequence: camera matrices from T (unless base.camera_matrices_valid) -> forward -> exact residual pass beside
+ * the per-splat Jacobian preparation (three planes f, df/da, df/db and per-workgroup L1 partials into `scratch`) ->
+ * Jacobian-only backward in sketch mode -> normal equations (44 fp32 partial sums per workgroup) -> fp64 sum in index
+ * order, Cholesky, lambda rule, best record, step.  No atomics and no memset anywhere: two calls on the same inputs
+ * give the same bits.  `scratch` holds mgs_gauss_newton_scratch_bytes(&base.fwd.shape) bytes and needs no initial state.
+ * normal_out (or NULL) receives the 44 sums of this iteration as floats: the upper triangle of H row-major
+ * (H00 .. H07, H11 .. H17, ..., H77; WITHOUT lambda), then g[8] (the sign of sum J f: the solve negates it). */
+typedef struct mgs_tracking_gn_args {
+  mgs_tracking_iter_args base;   /* as for mgs_tracking_iteration_second_order */
+  int32_t stack_dim, sketch_dim; /* of the configured sketch: only their product enters (s above) */
+  void* sketch_ws;               /* sketch_bytes of backward scratch */
+  void* scratch;                 /* mgs_gauss_newton_scratch_bytes */
+  mgs_lm_step_args lm;           /* SJ / Sf / sj_* / rows / loss / zero_after are ignored */
+  float* normal_out;             /* [44] or NULL */
+} mgs_tracking_gn_args;
+
+int32_t mgs_tracking_gn_args_size(void);
+uint64_t mgs_gauss_newton_scratch_bytes(const mgs_raster_shape* shape);
+int32_t mgs_tracking_iteration_gauss_newton(const mgs_tracking_gn_args* args, void* stream);
+/* ... with the stacked RGB-D objective (mgs_tracking_depth_args as for mgs_tracking_iteration_second_order_rgbd) */
+int32_t mgs_tracking_iteration_gauss_newton_rgbd(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* depth,
+                                                 void* stream);
+/* The same sequence up to the sums: normal_out (required) is written, nothing is solved and neither the pose, the
+ * exposure, lm_state nor best is touched (the lm block may be zero).  depth may be NULL (monocular). */
+int32_t mgs_normal_equations(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* depth, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

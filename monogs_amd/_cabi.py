@@ -33,6 +33,8 @@ EXPORTS = (
     "mgs_frame_prepare_args_size", "mgs_frame_prepare_scratch_bytes", "mgs_frame_prepare",
     "mgs_remap_build_args_size", "mgs_frame_remap_args_size", "mgs_remap_build", "mgs_frame_prepare_remapped",
     "mgs_stereo_depth_args_size", "mgs_stereo_scratch_bytes", "mgs_stereo_depth",
+    "mgs_tracking_gn_args_size", "mgs_gauss_newton_scratch_bytes", "mgs_tracking_iteration_gauss_newton",
+    "mgs_tracking_iteration_gauss_newton_rgbd", "mgs_normal_equations",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -143,6 +145,14 @@ class TrackingSOArgs(C.Structure):
     _fields_ = [("base", TrackingIterArgs), ("stack_dim", C.c_int32), ("sketch_dim", C.c_int32),
                 ("key", C.c_uint64), ("bucket", _fp), ("weights", _fp), ("accum", _fp),
                 ("sketch_ws", _fp), ("lm", LMStepArgs), ("scratch_kept_zero", C.c_int32), ("repeat_dim", C.c_int32)]
+
+
+class TrackingGNArgs(C.Structure):
+    _fields_ = [("base", TrackingIterArgs), ("stack_dim", C.c_int32), ("sketch_dim", C.c_int32),
+                ("sketch_ws", _fp), ("scratch", _fp), ("lm", LMStepArgs), ("normal_out", _fp)]
+
+
+NORMAL_SUMS = 44           # upper triangle of H (36, row-major, i <= j) then g (8)
 
 
 ADAM_MAX_GROUPS = 8
@@ -444,6 +454,17 @@ def lib():
     L.mgs_stereo_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     L.mgs_stereo_depth.restype = C.c_int32
     L.mgs_stereo_depth.argtypes = [C.POINTER(StereoDepthArgs), C.c_void_p]
+    L.mgs_tracking_gn_args_size.restype, L.mgs_tracking_gn_args_size.argtypes = C.c_int32, []
+    if L.mgs_tracking_gn_args_size() != C.sizeof(TrackingGNArgs):
+        raise NativeLibraryError("TrackingGNArgs does not have the size of mgs_tracking_gn_args")
+    L.mgs_gauss_newton_scratch_bytes.restype = C.c_uint64
+    L.mgs_gauss_newton_scratch_bytes.argtypes = [C.POINTER(RasterShape)]
+    L.mgs_tracking_iteration_gauss_newton.restype = C.c_int32
+    L.mgs_tracking_iteration_gauss_newton.argtypes = [C.POINTER(TrackingGNArgs), C.c_void_p]
+    L.mgs_tracking_iteration_gauss_newton_rgbd.restype = C.c_int32
+    L.mgs_tracking_iteration_gauss_newton_rgbd.argtypes = [C.POINTER(TrackingGNArgs), _dp, C.c_void_p]
+    L.mgs_normal_equations.restype = C.c_int32
+    L.mgs_normal_equations.argtypes = [C.POINTER(TrackingGNArgs), _dp, C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -654,6 +654,111 @@ __global__ __launch_bounds__(kBucketThreads) void k_sketch_bucket(KP P, KB B) {
 }
 
 // ---------------------------------------------------------------------------------
+// Dense Gauss-Newton iteration (mgs_tracking_iteration_gauss_newton): the exact residual pass beside the per-splat
+// preparation (k_sketch_prep_residual's arrangement, without its LDS bucket table), k_blend_bwd<true, true> unchanged,
+// and k_normal_eq in place of k_sketch_bucket: the per-pixel rows never leave the registers.
+template <bool DEPTH>
+__global__ __launch_bounds__(kPreBlock) void k_normal_prep_residual(KP P, KB B, mgs_sketch_residual_args A, SketchExact E,
+                                                                    int res_blocks, mgs_tracking_depth_args D) {
+  __shared__ float s_red[kSketchThreads / 64];
+  if ((int)blockIdx.x < res_blocks)
+    sketch_residual_block<DEPTH, true>(A, SketchKeys{0, 0, 0, 0u, 0u, 0u}, nullptr, s_red, blockIdx.x, res_blocks, &D, &E);
+  else sketch_prep_gaussian(P, B, ((int)blockIdx.x - res_blocks) * kPreBlock + threadIdx.x);
+}
+
+struct KN {
+  const float* planes;     // [3][H*W]: f, df/da, df/db of the exact residual pass
+  float* partial;          // [gridDim.x][kNormalSums]: upper triangle of sum J J^T (36, row-major, i <= j), then sum J f (8)
+};
+
+// Per tile: per-pixel rows = sum of the tile's slabs, as in k_sketch_bucket (same persistent workgroups, a tile per
+// 256-thread quarter, unconditional slab loads with the quadrant bit selecting the value).  The pixel's 8-column row
+// [J_tau(6), df/da, df/db] and its f go straight into 44 fp32 accumulators of the thread: 36 products of the upper
+// triangle of J J^T and 8 of J f.  The sums leave in a FIXED order - a shuffle tree across the wave, the 16 wave totals
+// through LDS in wave order, one plain store of 44 floats per workgroup - so that two launches on the same input give
+// the same bits.  No atomics.  A tile without backward items still counts: its pose columns are zero, its exposure
+// columns and f are not.
+__global__ __launch_bounds__(kBucketThreads) void k_normal_eq(KP P, KB B, KN N) {
+  __shared__ float s_red[kBucketThreads / 64][kNormalSums];
+  const size_t HW = (size_t)P.W * P.H;
+  const int sub = threadIdx.x >> 8, tid = threadIdx.x & 255, q = tid >> 6, lane = tid & 63;
+  float acc[kNormalSums];
+#pragma unroll
+  for (int i = 0; i < kNormalSums; i++) acc[i] = 0.f;
+  for (int tile = blockIdx.x * 4 + sub; tile < P.T; tile += gridDim.x * 4) {
+    const int a = P.seg_offset[tile], b = min(P.seg_offset[tile + 1], P.max_segs);
+    float row[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+#pragma unroll 4
+    for (int i = a; i < b; i = (i / kSketchReps + 1) * kSketchReps) {       // wave-uniform
+      const int sid = slab_index(i, tile);
+      const bool on = (B.slab_mask[sid] >> q) & 1u;
+      const float* slab = B.slabs + (size_t)sid * (6 * 256) + tid;
+#pragma unroll
+      for (int t = 0; t < 6; t++) {
+        const float v = slab[t * 256];
+        row[t] += on ? v : 0.f;
+      }
+    }
+    const int px = (tile % P.grid_x) * kTile + (lane & 7) + 8 * (q & 1);
+    const int py = (tile / P.grid_x) * kTile + (lane >> 3) + 8 * (q >> 1);
+    if (px >= P.W || py >= P.H) continue;
+    const size_t p = (size_t)py * P.W + px;
+    const float f = N.planes[p];
+    row[6] = N.planes[HW + p];
+    row[7] = N.planes[2 * HW + p];
+    int k = 0;
+#pragma unroll
+    for (int i = 0; i < 8; i++)
+#pragma unroll
+      for (int j = i; j < 8; j++) acc[k++] += row[i] * row[j];
+#pragma unroll
+    for (int i = 0; i < 8; i++) acc[36 + i] += row[i] * f;
+  }
+  const int wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int i = 0; i < kNormalSums; i++) {
+    float v = acc[i];
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off);
+    if ((threadIdx.x & 63) == 0) s_red[wave][i] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kNormalSums) {
+    float t = 0.f;
+#pragma unroll
+    for (int w = 0; w < kBucketThreads / 64; w++) t += s_red[w][threadIdx.x];
+    N.partial[(size_t)blockIdx.x * kNormalSums + threadIdx.x] = t;
+  }
+}
+
+// workgroups of k_normal_eq (and rows of its partials) for T tiles
+int normal_eq_blocks(int T) { return min(kBucketBlocks, (T + 3) / 4); }
+// workgroups of the exact residual pass (and entries of its L1 partials)
+int normal_residual_blocks(long long num_pixels) {
+  const long long want = (num_pixels + kSketchThreads - 1) / kSketchThreads;
+  return (int)(want < kSketchBlocks ? want : kSketchBlocks);
+}
+
+// residual pass + preparation, Jacobian-only blend backward, normal equations: three launches, no memset
+int launch_normal_backward(const KP& P, const KB& B, hipStream_t st, const mgs_sketch_residual_args& A,
+                           const mgs_tracking_depth_args* D, float* planes, float* l1_partial, float* partial) {
+  if ((unsigned long long)max(P.cap, 0) * (kPairStride * 4) > kPairBufferExtent) return MGS_ERR_UNSUPPORTED;
+  const int items = B.pair_bound > 0 ? (int)min((long long)P.max_segs, (long long)B.pair_bound / kItem + P.T) : P.max_segs;
+  const int prep_blocks = (P.N + kPreBlock - 1) / kPreBlock;
+  const int res_blocks = normal_residual_blocks(A.num_pixels);
+  const SketchExact E = {planes, l1_partial};
+  if (D)
+    launch("normal_prep_residual_rgbd", k_normal_prep_residual<true>, dim3(res_blocks + prep_blocks), dim3(kPreBlock), st,
+           P, B, A, E, res_blocks, *D);
+  else
+    launch("normal_prep_residual", k_normal_prep_residual<false>, dim3(res_blocks + prep_blocks), dim3(kPreBlock), st,
+           P, B, A, E, res_blocks, mgs_tracking_depth_args{});
+  launch("blend_bwd_sketch", k_blend_bwd<true, true>, dim3(grid_pad((items + kSketchReps - 1) / kSketchReps, kBwdChunk)), dim3(64), st, P, B);
+  const KN N = {planes, partial};
+  launch("normal_eq", k_normal_eq, dim3(normal_eq_blocks(P.T)), dim3(kBucketThreads), st, P, B, N);
+  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
+// ---------------------------------------------------------------------------------
 // MAP (mapping mode, mgs_map_accum_args): instead of storing the gradients w.r.t. the activated
 // attributes of this view, chain them through GaussianModel's activations
 // (gaussian_model.py:54-62: scaling = exp, opacity = sigmoid, rotation = normalize) and

@@ -30,6 +30,12 @@ namespace mgs {
 int launch_forward_project(const KP& P, hipStream_t st);
 int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD = nullptr);
 int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_reduce, const SketchFuse* fuse);
+int launch_normal_backward(const KP& P, const KB& B, hipStream_t st, const mgs_sketch_residual_args& A,
+                           const mgs_tracking_depth_args* D, float* planes, float* l1_partial, float* partial);
+int normal_eq_blocks(int T);
+int normal_residual_blocks(long long num_pixels);
+int launch_lm_solve_normal(const mgs_lm_step_args& L, const float* partial, int nblk, const float* l1_partial, int nl1,
+                           float* normal_out, float* l1_out, int solve, hipStream_t st);
 int launch_visibility(const int* n_touched, unsigned char* vis, int n, hipStream_t st);
 int launch_radii_fold(const int* radii, float* max_radii, int n, hipStream_t st);
 }  // namespace mgs
@@ -674,7 +680,110 @@ static int32_t tracking_iteration_so_impl(const mgs_tracking_so_args* args, cons
   return MGS_OK;
 }
 
+// scratch of the dense Gauss-Newton iteration: planes [3][HW] | normal-equation partials | L1 partials | L1 total
+namespace {
+struct GnLayout { uint64_t planes, partial, l1_partial, l1, bytes; };
+GnLayout gn_layout(const mgs_raster_shape& s) {
+  GnLayout L;
+  const uint64_t HW = (uint64_t)s.width * s.height;
+  const uint64_t T = (uint64_t)((s.width + kTile - 1) / kTile) * ((s.height + kTile - 1) / kTile);
+  uint64_t o = 0;
+  L.planes = o; o = align_up(o + 3 * HW * 4);
+  L.partial = o; o = align_up(o + (uint64_t)normal_eq_blocks((int)T) * kNormalSums * 4);
+  L.l1_partial = o; o = align_up(o + (uint64_t)normal_residual_blocks((long long)HW) * 4);
+  L.l1 = o; o = align_up(o + 16);
+  L.bytes = o;
+  return L;
+}
+}  // namespace
+
+// solve == 0: mgs_normal_equations (the sums only)
+static int32_t gauss_newton_impl(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* D, void* stream,
+                                 int solve) {
+  if (!args) return MGS_ERR_BAD_ARGUMENT;
+  const mgs_tracking_iter_args& b = args->base;
+  if (!b.bwd || !b.grad_image || !b.fwd.viewmatrix || !b.fwd.projmatrix || b.fwd.shape.pair_capacity < 1 ||
+      !args->sketch_ws || !args->scratch || args->stack_dim < 1 || args->sketch_dim < 1 || !b.loss.gt ||
+      !b.loss.exposure_a || !b.loss.exposure_b || !shape_ok(b.fwd.shape))
+    return MGS_ERR_BAD_ARGUMENT;
+  if (!b.camera_matrices_valid && !b.adam.T) return MGS_ERR_BAD_ARGUMENT;
+  if (solve ? (!b.adam.T || !args->lm.lm_state || !args->lm.x_out || !(args->lm.increase_factor > 0.f) ||
+               !(args->lm.decrease_factor > 0.f))
+            : !args->normal_out)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (D && !depth_args_ok(D)) return MGS_ERR_BAD_ARGUMENT;
+  hipStream_t st = (hipStream_t)stream;
+  int32_t rc = MGS_OK;
+  if (!b.camera_matrices_valid) {
+    rc = mgs_camera_from_pose(b.adam.T, b.fwd.projmatrix_raw, const_cast<float*>(b.fwd.viewmatrix),
+                              const_cast<float*>(b.fwd.projmatrix), stream);
+    if (rc != MGS_OK) return rc;
+  }
+  if ((rc = mgs_raster_forward_project(&b.fwd, stream)) != MGS_OK) return rc;
+  if ((rc = mgs_raster_forward_blend(&b.fwd, stream)) != MGS_OK) return rc;
+  KP P;
+  if ((rc = fill_kp(b.fwd, true, false, P)) != MGS_OK) return rc;
+  const Layout L = make_layout(b.fwd.shape);
+  const GnLayout G = gn_layout(b.fwd.shape);
+  const int64_t HW = (int64_t)P.W * P.H;
+  char* gs = (char*)args->scratch;
+  float* planes = (float*)(gs + G.planes);
+  float* partial = (float*)(gs + G.partial);
+  float* l1_partial = (float*)(gs + G.l1_partial);
+  float* l1 = (float*)(gs + G.l1);
+  KB B;
+  memset(&B, 0, sizeof(B));
+  B.grad_color = b.grad_image; B.grad_depth = D ? D->grad_depth : nullptr;
+  B.pair_grad = (float*)((char*)b.bwd + L.pair_grad);
+  B.tau_partial = (float*)((char*)b.bwd + L.tau_partial);
+  B.sketch_mode = 1; B.sketch_only = 1; B.sketch_dim = args->sketch_dim; B.stack_dim = args->stack_dim;
+  char* sw = (char*)args->sketch_ws;
+  B.slabs = (float*)(sw + L.slabs);
+  B.slab_mask = (unsigned int*)(sw + L.slab_mask);
+  B.splat_jac = (float*)(sw + L.splat_jac);
+  mgs_sketch_residual_args Rr;
+  memset(&Rr, 0, sizeof(Rr));
+  Rr.image = b.fwd.out_color; Rr.opacity = b.fwd.out_opacity; Rr.gt = b.loss.gt; Rr.mask = b.loss.mask;
+  Rr.exposure_a = b.loss.exposure_a; Rr.exposure_b = b.loss.exposure_b;
+  Rr.exposure_eps = b.loss.exposure_eps; Rr.huber_delta = b.loss.huber_delta; Rr.num_pixels = HW;
+  Rr.stack_dim = args->stack_dim; Rr.sketch_dim = args->sketch_dim;
+  Rr.grad_image = b.grad_image;
+  mgs_tracking_depth_args Dd;
+  if (D) { Dd = *D; Dd.depth = b.fwd.out_depth; }
+  if ((rc = launch_normal_backward(P, B, st, Rr, D ? &Dd : nullptr, planes, l1_partial, partial)) != MGS_OK) return rc;
+  mgs_lm_step_args S = args->lm;
+  S.SJ = nullptr; S.sj_tau = nullptr; S.sj_exposure = nullptr; S.Sf = nullptr; S.rows = 0; S.loss = l1;
+  S.T = b.adam.T; S.exposure_a = b.adam.exposure_a; S.exposure_b = b.adam.exposure_b;
+  S.best = b.best;
+  S.zero_after = nullptr; S.zero_count = 0;
+  S.projection = b.fwd.projmatrix_raw;
+  S.viewmatrix_out = const_cast<float*>(b.fwd.viewmatrix);
+  S.projmatrix_out = const_cast<float*>(b.fwd.projmatrix);
+  return launch_lm_solve_normal(S, partial, normal_eq_blocks(P.T), l1_partial, normal_residual_blocks(HW),
+                                args->normal_out, l1, solve, st);
+}
+
 extern "C" {
+
+int32_t mgs_tracking_gn_args_size(void) { return (int32_t)sizeof(mgs_tracking_gn_args); }
+
+uint64_t mgs_gauss_newton_scratch_bytes(const mgs_raster_shape* shape) {
+  return shape && shape_ok(*shape) ? gn_layout(*shape).bytes : 0;
+}
+
+int32_t mgs_tracking_iteration_gauss_newton(const mgs_tracking_gn_args* args, void* stream) {
+  return gauss_newton_impl(args, nullptr, stream, 1);
+}
+
+int32_t mgs_tracking_iteration_gauss_newton_rgbd(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* depth,
+                                                 void* stream) {
+  if (!depth_args_ok(depth)) return MGS_ERR_BAD_ARGUMENT;
+  return gauss_newton_impl(args, depth, stream, 1);
+}
+
+int32_t mgs_normal_equations(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* depth, void* stream) {
+  return gauss_newton_impl(args, depth, stream, 0);
+}
 
 int32_t mgs_tracking_iteration_second_order(const mgs_tracking_so_args* args, void* stream) {
   return tracking_iteration_so_impl(args, nullptr, stream);

@@ -44,13 +44,26 @@ struct SketchKeys { int on, chunk, bits; unsigned int k0, k1, k2; };   // on != 
 // 3 * stack * sketch floats of LDS ([d][3]: Sf, d/da, d/db), s_red = kSketchThreads / 64 floats.
 // DEPTH (RGB-D tracking, include/monogs_raster.h: mgs_tracking_depth_args): the colour rows take the factor w_rgb and
 // the depth row r_d joins the pixel's bucket sum - loss_tracking_img.sum(dim=0) of slam_frontend.py:640 over four rows.
-template <bool DEPTH = false>
+// EXACT (dense Gauss-Newton iteration, DESIGN.md "Dense Gauss-Newton tracking"): no bucket, no sign - every pixel keeps
+// its own row.  f_p, df_p/da and df_p/db leave as three planes, the L1 criterion as one partial per workgroup; A.bucket /
+// weights / Sf / sj_exposure / l1, K, s_acc are not touched and nothing is accumulated with atomics.
+constexpr int kNormalSums = 44;   // upper triangle of the 8 x 8 normal matrix (36) + right-hand side (8)
+
+struct SketchExact {
+  float* planes;        // [3][H*W]: f, df/da, df/db
+  float* l1_partial;    // [nblocks]
+};
+
+template <bool DEPTH = false, bool EXACT = false>
 __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_args& A, const SketchKeys& K, float* s_acc,
                                                       float* s_red, int bid, int nblocks,
-                                                      const mgs_tracking_depth_args* D = nullptr) {
+                                                      const mgs_tracking_depth_args* D = nullptr,
+                                                      const SketchExact* E = nullptr) {
   const int d = A.stack_dim * A.sketch_dim;
-  for (int i = threadIdx.x; i < 3 * d; i += kSketchThreads) s_acc[i] = 0.f;
-  __syncthreads();
+  if constexpr (!EXACT) {
+    for (int i = threadIdx.x; i < 3 * d; i += kSketchThreads) s_acc[i] = 0.f;
+    __syncthreads();
+  }
   // The sketched path goes through the reference's hand-written ApplyExposure.backward (utils/slam_utils.py:145-149),
   // which is NOT the exact derivative of (|a| + eps) image + b: grad_image = |a| grad (no eps) and
   // grad_a = sum(grad image) (no sign(a)).  Followed to the letter here (pinned by tests/golden/map_update_ref.npz:
@@ -63,9 +76,10 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
   float l1 = 0.f;
   for (size_t p = (size_t)bid * kSketchThreads + threadIdx.x; p < HW; p += (size_t)nblocks * kSketchThreads) {
     const float om = A.opacity[p] * (A.mask ? A.mask[p] : 1.f);
-    int b;
-    float wsign;
-    if (K.on) {    // the partition of mgs_sketch_assign, evaluated (and left behind for the backward) in this pass
+    int b = -1;
+    float wsign = 1.f;
+    if constexpr (EXACT) {
+    } else if (K.on) {    // the partition of mgs_sketch_assign, evaluated (and left behind for the backward) in this pass
       const unsigned int pmask = K.bits >= 32 ? 0xFFFFFFFFu : ((1u << K.bits) - 1u);
       unsigned int x = (unsigned int)p;
       do { x = perm_round(x, pmask, K.bits, K.k0, K.k1); } while ((size_t)x >= HW);
@@ -102,7 +116,11 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
       hs += huber(rd, A.huber_delta, dh);
       D->grad_depth[p] = w * dh * D->w_depth * dm;
     }
-    if (b >= 0 && b < d) {
+    if constexpr (EXACT) {
+      E->planes[p] = w * hs;
+      E->planes[HW + p] = da;
+      E->planes[2 * HW + p] = db;
+    } else if (b >= 0 && b < d) {
       atomicAdd(&s_acc[3 * b], w * hs);
       atomicAdd(&s_acc[3 * b + 1], da);
       atomicAdd(&s_acc[3 * b + 2], db);
@@ -116,8 +134,10 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
   if (threadIdx.x == 0) {
     float t = 0.f;
     for (int w = 0; w < kSketchThreads / 64; w++) t += s_red[w];
-    atomicAdd(A.l1, t);
+    if constexpr (EXACT) E->l1_partial[bid] = t;
+    else atomicAdd(A.l1, t);
   }
+  if constexpr (EXACT) return;
   __syncthreads();
   for (int i = threadIdx.x; i < d; i += kSketchThreads) {
     const float f = s_acc[3 * i], x = s_acc[3 * i + 1], y = s_acc[3 * i + 2];

@@ -496,6 +496,11 @@ __global__ __launch_bounds__(kLossBlock) void k_track_loss_rgbd_finish(mgs_track
 // (:49-53): T <- Exp(x[:6]) T, exposure += x[6:8].  One workgroup: fp64 row reduction,
 // 8x8 Cholesky by thread 0.  (torch.linalg.lstsq on this 1032x8 problem costs ~3.7 ms of
 // host-side solver setup per call.)
+// lm_solve_tail: what thread 0 does once the 36 + 8 sums exist (sum(k): upper triangle of SJ^T SJ row-major, then SJ^T Sf) -
+// lambda rule, Cholesky, best record, step.  Shared with k_lm_solve_normal, whose sums come from k_normal_eq.
+template <class Sum>
+__device__ __forceinline__ void lm_solve_tail(const mgs_lm_step_args& A, float loss_in, Sum sum);
+
 __global__ __launch_bounds__(256) void k_lm_solve_step(mgs_lm_step_args A) {
   __shared__ double s_red[4][44];
   const float loss_in = A.loss ? A.loss[0] : 0.f;     // read before the accumulators are zeroed below
@@ -533,12 +538,17 @@ __global__ __launch_bounds__(256) void k_lm_solve_step(mgs_lm_step_args A) {
   if (A.zero_after)
     for (int i = threadIdx.x; i < A.zero_count; i += 256) A.zero_after[i] = 0.f;
   if (threadIdx.x != 0) return;
+  lm_solve_tail(A, loss_in, [&](int k) { return s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k]; });
+}
+
+template <class Sum>
+__device__ __forceinline__ void lm_solve_tail(const mgs_lm_step_args& A, float loss_in, Sum sum) {
   if (A.lm_state && A.lm_state[3] != 0.f) return;      // converged earlier: the reference has left its loop
   double H[8][8], g[8];
   int k = 0;
   for (int i = 0; i < 8; i++)
     for (int j = i; j < 8; j++) {
-      const double v = s_red[0][k] + s_red[1][k] + s_red[2][k] + s_red[3][k];
+      const double v = sum(k);
       H[i][j] = v; H[j][i] = v;
       k++;
     }
@@ -552,7 +562,7 @@ __global__ __launch_bounds__(256) void k_lm_solve_step(mgs_lm_step_args A) {
     A.lm_state[0] = lambda; A.lm_state[1] = loss; A.lm_state[2] = 1.f;
   }
   for (int i = 0; i < 8; i++) {
-    g[i] = -(s_red[0][36 + i] + s_red[1][36 + i] + s_red[2][36 + i] + s_red[3][36 + i]);
+    g[i] = -sum(36 + i);
     H[i][i] += (double)lambda;
   }
   // Cholesky H = L L^T (lambda > 0 makes H positive definite)
@@ -626,6 +636,33 @@ __global__ __launch_bounds__(256) void k_lm_solve_step(mgs_lm_step_args A) {
   }
   if (A.exposure_a) A.exposure_a[0] += (float)x[6];
   if (A.exposure_b) A.exposure_b[0] += (float)x[7];
+}
+
+// Dense Gauss-Newton step (mgs_tracking_iteration_gauss_newton): the 36 + 8 sums are the per-workgroup partials of
+// k_normal_eq ([nblk][44]), the L1 criterion the per-workgroup partials of the exact residual pass ([nl1]).  Each of the
+// 45 totals is ONE thread's fp64 sum in index order (the loads are independent, the additions are not), so the
+// step depends on nothing but the inputs' bits.  normal_out (or NULL): the 44 totals as floats.  solve == 0
+// (mgs_normal_equations): totals only.
+__global__ __launch_bounds__(128) void k_lm_solve_normal(mgs_lm_step_args A, const float* partial, int nblk, const float* l1_partial,
+                                                         int nl1, float* normal_out, float* l1_out, int solve) {
+  __shared__ double s_sum[kNormalSums + 1];
+  const int t = threadIdx.x;
+  if (t < kNormalSums) {
+    double v = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < nblk; b++) v += (double)partial[(size_t)b * kNormalSums + t];
+    s_sum[t] = v;
+    if (normal_out) normal_out[t] = (float)v;
+  } else if (t == 64) {
+    double v = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < nl1; b++) v += (double)l1_partial[b];
+    s_sum[kNormalSums] = v;
+    if (l1_out) l1_out[0] = (float)v;
+  }
+  __syncthreads();
+  if (t != 0 || !solve) return;
+  lm_solve_tail(A, (float)s_sum[kNormalSums], [&](int k) { return s_sum[k]; });
 }
 
 // ---------------------------------------------------------------------------------
@@ -899,6 +936,13 @@ __global__ __launch_bounds__(kSketchThreads) void k_sketch_residual_rgbd(mgs_ske
 static int loss_blocks(int64_t hw) {
   const int64_t b = (hw + kLossBlock - 1) / kLossBlock;
   return (int)(b < kLossBlocks ? (b < 1 ? 1 : b) : kLossBlocks);
+}
+
+int launch_lm_solve_normal(const mgs_lm_step_args& L, const float* partial, int nblk, const float* l1_partial, int nl1,
+                           float* normal_out, float* l1_out, int solve, hipStream_t st) {
+  launch("lm_solve_normal", k_lm_solve_normal, dim3(1), dim3(128), st, L, partial, nblk, l1_partial, nl1, normal_out,
+         l1_out, solve);
+  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 }  // namespace mgs

@@ -109,6 +109,14 @@ def sampled_num_pixels(config=DEFAULT_CONFIG) -> int:
     return -1 if n is None else int(n)
 
 
+def second_order_exact(config=DEFAULT_CONFIG) -> bool:
+    """RGN.second_order.exact of a config: True turns the second-order iterations into dense Gauss-Newton steps (every
+    pixel its own row, no sketch; DESIGN.md "Dense Gauss-Newton tracking"); False when absent."""
+    so = (config.get("Training", {}).get("RGN", {}) or {}).get("second_order", {}) or {}
+    v = so.get("exact", False)
+    return False if v is None else bool(v)
+
+
 def make_pose_optimizer(viewpoint: ViewCamera, config=DEFAULT_CONFIG):
     lr = config["Training"]["lr"]
     return torch.optim.Adam([
@@ -232,19 +240,110 @@ def sketch_args_from_buckets(bucket: torch.Tensor, weights: torch.Tensor, height
             "chunk_size": chunk, "rand_weights": weights.reshape(R, height, width).float()}
 
 
+IDENTITY_PASS_PIXELS = 2048      # buckets of one identity pass: 2048 x 6 floats of bucket table fit in LDS
+
+
+def identity_sketch_args(height, width, device, pass_pixels=IDENTITY_PASS_PIXELS):
+    """forward_sketch_args whose buckets are single pixels: pass k (a `repeat` of the sketch path) makes the pixels
+    [k * pass_pixels, (k + 1) * pass_pixels) their own buckets 0 .. pass_pixels - 1 of one stack and leaves every other
+    pixel out (-1); all weights are +1; ceil(H * W / pass_pixels) passes.  The slots of the last pass past H * W point
+    at pixel 0 in rand_indices (the exposure rows need a rectangular table) and belong to no pixel in sketch_indices:
+    harvest_pixel_rows drops them."""
+    m = height * width
+    passes = (m + pass_pixels - 1) // pass_pixels
+    p = torch.arange(passes * pass_pixels, device=device)
+    inside = p < m
+    src = torch.where(inside, p, torch.zeros_like(p))
+    idx = torch.full((passes, m), -1, dtype=torch.int32, device=device)
+    idx[(p // pass_pixels)[inside], p[inside]] = (p % pass_pixels)[inside].to(torch.int32)
+    rows = (src // width).view(passes, 1, pass_pixels, 1).to(torch.int32)
+    cols = (src % width).view(passes, 1, pass_pixels, 1).to(torch.int32)
+    return {"sketch_mode": 1, "repeat_dim": passes, "stack_dim": 1, "sketch_dim": pass_pixels,
+            "sketch_indices": idx.view(passes, 1, height, width),
+            "rand_indices": (rows, cols), "rand_indices_row": rows, "rand_indices_col": cols,
+            "sketch_dtau": torch.empty(1, pass_pixels, 6, device=device, requires_grad=True),
+            "sketch_dexposure": torch.empty(1, pass_pixels, 2, device=device, requires_grad=True),
+            "chunk_size": 1, "rand_weights": torch.ones(1, height, width, device=device)}
+
+
+def harvest_pixel_rows(viewpoint, gaussians, background, scale_dim, pipe=Pipe, config=DEFAULT_CONFIG, residual_fn=None,
+                       pass_pixels=IDENTITY_PASS_PIXELS):
+    """Per-pixel rows of the second-order objective through the EXISTING sketch path (identity_sketch_args): one render,
+    ceil(H W / pass_pixels) backward passes.  f_p = s * sum_c Huber(r_pc) with s = scale_dim / (H W) (scale_dim =
+    stack_dim * sketch_dim of the configured sketch) and J_p = d f_p / d [rho; theta; a; b], the exposure columns by
+    ApplyExposure's hand-written backward.  Returns (l1, f [H W], J [H W, 8], render_pkg), detached."""
+    residual_fn = get_loss_tracking_per_pixel if residual_fn is None else residual_fn
+    H, W = viewpoint.image_height, viewpoint.image_width
+    m = H * W
+    fsa = identity_sketch_args(H, W, viewpoint.device, pass_pixels)
+    render_pkg = render(viewpoint, gaussians, pipe, background, forward_sketch_args=fsa)
+    res = residual_fn(config, render_pkg["render"], render_pkg["depth"], render_pkg["opacity"], viewpoint,
+                      forward_sketch_args=fsa)
+    l1 = res.detach().abs().sum()
+    rgn = config["Training"]["RGN"]
+    if rgn["use_huber"]:
+        res = HuberLoss.apply(res, rgn["huber_delta"])
+    f = res.sum(dim=0) / (m / scale_dim)
+    J = torch.empty(fsa["repeat_dim"] * pass_pixels, 8, device=f.device)
+    for i in range(fsa["repeat_dim"]):
+        for p in (viewpoint.cam_rot_delta, viewpoint.cam_trans_delta, viewpoint.exposure_a, viewpoint.exposure_b,
+                  fsa["sketch_dtau"], fsa["sketch_dexposure"]):
+            p.grad = None
+        f.backward(gradient=torch.ones_like(f), retain_graph=True)
+        J[i * pass_pixels:(i + 1) * pass_pixels, :6] = fsa["sketch_dtau"].grad[0]
+        J[i * pass_pixels:(i + 1) * pass_pixels, 6:] = fsa["sketch_dexposure"].grad[0]
+    for p in (viewpoint.cam_rot_delta, viewpoint.cam_trans_delta, viewpoint.exposure_a, viewpoint.exposure_b):
+        p.grad = None
+    return l1, f.detach().reshape(-1), J[:m].detach(), render_pkg
+
+
+def sketch_rows(J, f, bucket, weights, num_buckets):
+    """CountSketch of per-pixel rows: SJ[b] = sum of weights_p J_p, Sf[b] = sum of weights_p f_p over the pixels with
+    bucket[p] == b (bucket[p] = -1: in no bucket) - what the sketched iteration forms without ever holding J."""
+    on = bucket >= 0
+    b = bucket[on].long()
+    w = weights[on].to(J.dtype)
+    SJ = torch.zeros(num_buckets, J.shape[1], dtype=J.dtype, device=J.device).index_add_(0, b, J[on] * w[:, None])
+    Sf = torch.zeros(num_buckets, dtype=f.dtype, device=f.device).index_add_(0, b, f[on] * w)
+    return SJ, Sf
+
+
+def normal_equations_from_rows(J, f):
+    """(H [8, 8], g [8]) = (J^T J, J^T f) in fp64: the dense Gauss-Newton system of the rows."""
+    Jd, fd = J.double(), f.double()
+    return Jd.T @ Jd, Jd.T @ fd
+
+
 def tracking_step_second_order(viewpoint, gaussians, background, lambda_, repeat_dim=1,
                                stack_dim=16, sketch_dim=64, pipe=Pipe, config=DEFAULT_CONFIG,
-                               generator=None, fused_solve=False, fsa=None, return_pkg=False, residual_fn=None):
+                               generator=None, fused_solve=False, fsa=None, return_pkg=False, residual_fn=None,
+                               exact=False):
     """One sketched Levenberg-Marquardt iteration (slam_frontend.py:484-710): sketched
     render, bucket-summed residual Sf, `repeat_dim` backward passes harvesting the sketched
     Jacobian SJ[(repeat*stack*sketch), 8], damped least squares, left-multiplicative pose
     step and exposure step.  `lambda_` is the damping, or a callable that maps this render's L1
     residual (the reference's loss_tracking_scalar) to it - the trust-region rule of :536-545 needs
     the current loss before the solve.  `residual_fn` as for tracking_step_first_order (the sum over the residual's
-    rows, :640, takes a depth row like a colour row).  Returns (l1, x, SJ, Sf[, render_pkg])."""
+    rows, :640, takes a depth row like a colour row).  Returns (l1, x, SJ, Sf[, render_pkg]).
+    `exact`: the dense Gauss-Newton step instead - per-pixel rows from harvest_pixel_rows (scaled by stack_dim *
+    sketch_dim / (H W) like the sketched ones), H = J^T J and g = J^T f in fp64, (H + lambda I) x = -g, the same step;
+    SJ / Sf of the result are then J [H W, 8] and f [H W].  A small-image mirror: one backward pass per 2048 pixels."""
     residual_fn = get_loss_tracking_per_pixel if residual_fn is None else residual_fn
     H, W = viewpoint.image_height, viewpoint.image_width
     m, dper = H * W, stack_dim * sketch_dim
+    if exact:
+        if repeat_dim != 1:
+            raise ValueError("exact=True sums every pixel once: repeat_dim must be 1")
+        l1, f, J, render_pkg = harvest_pixel_rows(viewpoint, gaussians, background, dper, pipe, config, residual_fn)
+        if callable(lambda_):
+            lambda_ = lambda_(l1)
+        with torch.no_grad():
+            Hn, g = normal_equations_from_rows(J, f)
+            x = torch.linalg.solve(Hn + float(lambda_) * torch.eye(8, dtype=Hn.dtype, device=Hn.device), -g).float()
+            viewpoint.T.copy_(SE3_exp(x[:6]) @ viewpoint.T)
+            viewpoint.exposure_a += x[6]
+            viewpoint.exposure_b += x[7]
+        return (l1, x, J, f, render_pkg) if return_pkg else (l1, x, J, f)
     if fsa is None:
         fsa = gen_forward_sketch_args(H, W, repeat_dim, stack_dim, sketch_dim, viewpoint.device,
                                       generator)

@@ -175,7 +175,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
                  native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
-                 stereo_matcher=None):
+                 stereo_matcher=None, second_order_exact: bool = False):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -206,7 +206,9 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     `stereo_matcher`: a stereo_depth.StereoMatcher; every frame then carries a pair (`image`, `image_right`), its depth
     is the matcher's (one mgs_stereo_depth call when its camera is made), the
     camera's image is the matcher's rectified left image, and from there the run is `sensor_depth=True`'s with that
-    depth in the place of `frame.depth` - what the reference's stereo dataset hands its frontend."""
+    depth in the place of `frame.depth` - what the reference's stereo dataset hands its frontend.
+    `second_order_exact` (slam_loops.second_order_exact reads it from a config): the second-order iterations are dense
+    Gauss-Newton steps (NativeTracker.enable_second_order(exact=True)) instead of sketched ones."""
     if stereo_matcher is not None:
         if any(getattr(f, "image_right", None) is None for f in frames):
             raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
@@ -314,7 +316,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                             num_pixels=num_pixels, sample_seed=seed + k,
                             mask=vp.rgb_pixel_mask if track_on_edges else None)
         if second_order_iters > 0:
-            trk.enable_second_order(stack_dim=16, sketch_dim=64, initial_lambda=1e-3, seed=seed + k)
+            trk.enable_second_order(stack_dim=16, sketch_dim=64, initial_lambda=1e-3, seed=seed + k,
+                                    exact=second_order_exact)
         # one frame of the reference's loop incl. its best-iterate bookkeeping (slam_frontend.py:455-822;
         # use_first_order_best / use_best_loss as in configs/mono/tum/base_config.yaml:268-273); the
         # tracker's depth / opacity / n_touched buffers end up rendered at the best iterate

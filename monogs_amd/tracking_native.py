@@ -189,8 +189,12 @@ class NativeTracker:
     # ---- second order (sketched Levenberg-Marquardt, slam_frontend.py:455-710) ----------
     def enable_second_order(self, stack_dim=16, sketch_dim=64, initial_lambda=1e-3, max_lambda=1e7,
                             min_lambda=1e-6, increase_factor=5.0, decrease_factor=5.0,
-                            converged_threshold=1e-5, seed=0, keep_sketch=False, repeat_dim=1):
+                            converged_threshold=1e-5, seed=0, keep_sketch=False, repeat_dim=1, exact=False):
         """Allocate the sketch scratch; defaults are configs/mono/tum/base_config.yaml:255-268.
+        `exact` (Training.RGN.second_order.exact, slam_loops.second_order_exact): the dense Gauss-Newton mode - every
+        pixel is its own row, H = sum J^T J and g = sum J^T f over all pixels on the device, no sketch noise and no
+        atomics (DESIGN.md "Dense Gauss-Newton tracking").  stack_dim * sketch_dim still scales the rows (so that the
+        lambdas keep their meaning); repeat_dim must be 1; `normal_equations` reads (H, g) of the last iteration back.
         `keep_sketch`: leave Sf / SJ of the last iteration readable (`self.sketch`) - the accumulators are
         then cleared by memset launches at the start of an iteration instead of by their consumer at its end
         (four launches more per iteration).  `repeat_dim` (base_config.yaml:258): that many sketched backward
@@ -201,6 +205,29 @@ class NativeTracker:
         R = int(repeat_dim)
         if R < 1:
             raise ValueError("repeat_dim must be >= 1")
+        self.so_exact = bool(exact)
+        if self.so_exact:
+            if R != 1:
+                raise ValueError("exact=True sums every pixel once: repeat_dim must be 1")
+            gn = _cabi.TrackingGNArgs()
+            C.memmove(C.byref(gn.base), C.byref(self.args), C.sizeof(_cabi.TrackingIterArgs))
+            sizes = _cabi.workspace_sizes(gn.base.fwd.shape)
+            self.so_sketch_ws = torch.empty(int(sizes.sketch_bytes), dtype=torch.uint8, device=dev)
+            nbytes = int(_cabi.lib().mgs_gauss_newton_scratch_bytes(C.byref(gn.base.fwd.shape)))
+            self.gn_scratch = torch.empty(nbytes, dtype=torch.uint8, device=dev)      # (needs no initial state)
+            self.gn_normal = torch.zeros(_cabi.NORMAL_SUMS, device=dev)
+            self.lm_state = torch.tensor([initial_lambda, 0.0, 0.0, 0.0], device=dev)
+            self._lm_initial = self.lm_state.clone()
+            self.so_x = torch.zeros(8, device=dev)
+            gn.stack_dim, gn.sketch_dim = stack_dim, sketch_dim
+            gn.sketch_ws, gn.scratch = self.so_sketch_ws.data_ptr(), self.gn_scratch.data_ptr()
+            gn.normal_out = self.gn_normal.data_ptr()
+            gn.lm.lm_state, gn.lm.x_out = self.lm_state.data_ptr(), self.so_x.data_ptr()
+            gn.lm.increase_factor, gn.lm.decrease_factor = increase_factor, decrease_factor
+            gn.lm.min_lambda, gn.lm.max_lambda = min_lambda, max_lambda
+            gn.lm.converged_threshold = converged_threshold
+            self.so_args, self.so_d, self.so_seed, self.so_t, self.so_repeat = gn, d, int(seed), 0, 1
+            return
         so = _cabi.TrackingSOArgs()
         C.memmove(C.byref(so.base), C.byref(self.args), C.sizeof(_cabi.TrackingIterArgs))
         sizes = _cabi.workspace_sizes(so.base.fwd.shape)
@@ -226,7 +253,35 @@ class NativeTracker:
     def step_second_order(self):
         """Enqueue one sketched LM iteration: fresh random bucket partition, forward, sketched
         residual, sketch-mode backward, damped solve and pose / exposure step, all on the
-        device.  Returns lm_state = [lambda, ||residual||_1, 1, converged] (device tensor)."""
+        device.  Returns lm_state = [lambda, ||residual||_1, 1, converged] (device tensor).
+        With enable_second_order(exact=True): one dense Gauss-Newton iteration instead (no partition, no sketch:
+        exact residual pass, Jacobian-only backward, normal equations, the same solve and step)."""
+        so = self._sync_so_pointers()
+        self.so_t += 1
+        if self.so_exact:      # no partition to draw: the iteration has no random input
+            lib, depth = _cabi.lib(), self.depth_args
+            if depth is None:
+                _cabi.check(lib.mgs_tracking_iteration_gauss_newton(C.byref(so), self._stream()),
+                            "mgs_tracking_iteration_gauss_newton")
+            else:
+                _cabi.check(lib.mgs_tracking_iteration_gauss_newton_rgbd(C.byref(so), C.byref(depth), self._stream()),
+                            "mgs_tracking_iteration_gauss_newton_rgbd")
+            self._matrices_fresh = True
+            return self.lm_state
+        so.key = (self.so_seed * 0x9E3779B97F4A7C15 + self.so_t) & 0xFFFFFFFFFFFFFFFF
+        if self.depth_args is None:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order(C.byref(so), self._stream()),
+                        "mgs_tracking_iteration_second_order")
+        else:
+            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order_rgbd(C.byref(so), C.byref(self.depth_args),
+                                                                             self._stream()),
+                        "mgs_tracking_iteration_second_order_rgbd")
+        self._matrices_fresh = True      # the LM kernel wrote the matrices of the stepped pose
+        return self.lm_state
+
+    def _sync_so_pointers(self):
+        """The argument block of the second-order iteration (sketched or exact) with the pointers that may have been
+        replaced since enable_second_order brought up to date."""
         so = self.so_args
         self._sync_pose_pointer()
         # pointers that _alloc_bins may have replaced since enable_second_order
@@ -241,27 +296,47 @@ class NativeTracker:
         so.base.adam.T = self.args.adam.T
         so.base.best = self.args.best
         so.base.camera_matrices_valid = 1 if self._matrices_fresh else 0
-        self.so_t += 1
-        so.key = (self.so_seed * 0x9E3779B97F4A7C15 + self.so_t) & 0xFFFFFFFFFFFFFFFF
-        if self.depth_args is None:
-            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order(C.byref(so), self._stream()),
-                        "mgs_tracking_iteration_second_order")
-        else:
-            _cabi.check(_cabi.lib().mgs_tracking_iteration_second_order_rgbd(C.byref(so), C.byref(self.depth_args),
-                                                                             self._stream()),
-                        "mgs_tracking_iteration_second_order_rgbd")
-        self._matrices_fresh = True      # the LM kernel wrote the matrices of the stepped pose
-        return self.lm_state
+        return so
 
     @property
     def sketch(self):
         """(Sf [R d], SJ [R d, 8]) of the last second-order iteration (views / a small cat); needs
         enable_second_order(keep_sketch=True) - otherwise the LM kernel has zeroed them again."""
+        if self.so_exact:
+            raise RuntimeError("exact=True forms no sketch: read normal_equations instead")
         if self.so_args.scratch_kept_zero:
             raise RuntimeError("enable_second_order(keep_sketch=True) is needed to read the sketch back")
         d = self.so_d
         a = self.so_accum
         return a[:d], torch.cat((a[3 * d:9 * d].view(d, 6), a[d:3 * d].view(d, 2)), dim=1)
+
+    @staticmethod
+    def _unpack_normal(sums):
+        """44 sums (upper triangle of H row-major, then g) -> (H [8, 8] symmetric, g [8])."""
+        iu = torch.triu_indices(8, 8, device=sums.device)
+        H = torch.zeros(8, 8, device=sums.device, dtype=sums.dtype)
+        H[iu[0], iu[1]] = sums[:36]
+        H[iu[1], iu[0]] = sums[:36]
+        return H, sums[36:44].clone()
+
+    @property
+    def normal_equations(self):
+        """(H [8, 8], g [8]) of the last exact iteration: H = sum_p J_p^T J_p without lambda, g = sum_p J_p^T f_p
+        (the step solves (H + lambda I) x = -g); columns [rho(3), theta(3), a, b].  Needs enable_second_order(exact=True)."""
+        if not getattr(self, "so_exact", False):
+            raise RuntimeError("enable_second_order(exact=True) is needed to read the normal equations back")
+        return self._unpack_normal(self.gn_normal)
+
+    def compute_normal_equations(self):
+        """mgs_normal_equations at the current pose: render, exact residual pass, Jacobian-only backward and the sums,
+        WITHOUT a solve - pose, exposure, lm_state and the best record stay as they are.  Returns (H, g)."""
+        if not getattr(self, "so_exact", False):
+            raise RuntimeError("enable_second_order(exact=True) is needed")
+        self._sync_so_pointers()
+        depth = None if self.depth_args is None else C.byref(self.depth_args)
+        _cabi.check(_cabi.lib().mgs_normal_equations(C.byref(self.so_args), depth, self._stream()), "mgs_normal_equations")
+        self._matrices_fresh = True
+        return self._unpack_normal(self.gn_normal)
 
     def _sync_pose_pointer(self):
         """`viewpoint.T` may have been REBOUND to a new tensor by Python code between two native
