@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define MGS_ABI_VERSION 9
+#define MGS_ABI_VERSION 10
 
 typedef enum mgs_status {
   MGS_OK = 0,
@@ -318,7 +318,9 @@ int32_t mgs_pose_adam_step(const mgs_pose_adam_args* args, void* stream);
  * m = mask (float 0/1, or NULL), dm = gt_depth > depth_mask_threshold (threshold < 0: no
  * mask).  Monocular: w_rgb = 1, w_depth = 0; RGB-D: w_rgb = alpha, w_depth = 1 - alpha.
  * apply_exposure = 0 is `initialization=True`.  `partial` holds
- * mgs_tracking_loss_partial_count(num_pixels) floats. */
+ * mgs_mapping_loss_partial_count(num_pixels) floats: [4][n] block sums (n = the number of reduction blocks) -
+ * sum |colour residual|, sum |depth residual| (written by forward and fused), d/da, d/db (backward and fused) -
+ * and one int behind them, the ticket of partial_ticket_ready. */
 typedef struct mgs_mapping_loss_args {
   const float* image;        /* [3,H,W] */
   const float* gt;           /* [3,H,W] */
@@ -340,10 +342,11 @@ typedef struct mgs_mapping_loss_args {
   float* grad_depth;         /* [1,H,W] or NULL */
   float* grad_a;             /* [1] or NULL */
   float* grad_b;             /* [1] or NULL */
-  /* != 0: the caller guarantees that the int at partial[2 n] (n = partial count / 3) was zero when
-   * the call was enqueued (e.g. a scratch zeroed once and reused: every call restores the zero).
-   * mgs_mapping_loss_forward then sums the block partials in the workgroup that finishes last
-   * instead of launching a second kernel. */
+  /* != 0: the caller guarantees that the int at partial[4 n] (the last slot of the partial count) was zero
+   * when the call was enqueued (e.g. a scratch zeroed once and reused: every call restores the zero).
+   * mgs_mapping_loss_forward / mgs_mapping_loss_fused then sum the block partials in the workgroup that
+   * finishes last instead of launching a second kernel / leaving the sums to the consumer.
+   * mgs_mapping_loss_backward ignores it. */
   int32_t partial_ticket_ready;
   int32_t reserved0;
 } mgs_mapping_loss_args;
@@ -404,9 +407,9 @@ int32_t mgs_lm_solve_step(const mgs_lm_step_args* args, void* stream);
 /* Monocular tracking objective (utils/slam_utils.py:188-205, :58-75; norm at
  * utils/slam_frontend.py:596-598):
  *   loss = || Huber_delta( opacity * mask * ((|a| + eps) * image + b - gt) ) ||_p   (p = pnorm, below)
- * huber_delta <= 0 disables Huber.  `partial` holds mgs_tracking_loss_partial_count floats
- * (four per reduction block: forward sums, the two exposure-gradient sums, and - onepass only -
- * the block sums of |residual| before Huber),
+ * huber_delta <= 0 disables Huber.  `partial` holds mgs_tracking_loss_partial_count floats, [4][n] for n
+ * reduction blocks: [n] sum |h|^p (forward, onepass, rgbd_fused) | [n] d/da | [n] d/db (backward, onepass,
+ * rgbd_fused) | [n] sum |residual| before Huber (onepass, rgbd_fused); an entry leaves the other slots alone,
  * `scalars` 2 floats ([0] = loss, [1] = 1/loss) written by forward and read by backward. */
 typedef struct mgs_tracking_loss_args {
   const float* image;          /* [3,H,W] */
@@ -437,17 +440,11 @@ typedef struct mgs_tracking_loss_args {
 int32_t mgs_tracking_loss_partial_count(int64_t num_pixels);
 int32_t mgs_tracking_loss_forward(const mgs_tracking_loss_args* args, void* stream);
 int32_t mgs_tracking_loss_backward(const mgs_tracking_loss_args* args, void* stream);
-/* Forward + backward in two launches (no finish kernels): every workgroup of the backward sums
- * the forward's block sums itself; scalars[0] = loss; the exposure-gradient block partials are
- * left at partial[n .. 3n) ([2, n]: d/da then d/db, n = *num_blocks_out) for a consumer that
- * sums them (mgs_pose_adam_step: exposure_partials).  grad_a / grad_b are not written. */
-int32_t mgs_tracking_loss_fused(const mgs_tracking_loss_args* args, int32_t* num_blocks_out, void* stream);
 /* ONE launch: block sums of the squared residuals ([n] at partial), UN-normalised image gradient
  * (as if loss were 1) and un-normalised exposure partials ([2,n] at partial + n).  The consumer
  * (mgs_pose_adam_step with loss_norm_mode = 1) applies grad_out / loss.  args->scalars is not
  * written here.  partial + 3n: [n] block sums of |residual| BEFORE Huber (the best-iterate criterion
- * of utils/slam_frontend.py:510).  Replaces the two launches of mgs_tracking_loss_fused inside
- * mgs_tracking_iteration (reference: utils/slam_utils.py:188-217 get_loss_tracking_rgb + autograd). */
+ * of utils/slam_frontend.py:510).  (reference: utils/slam_utils.py:188-217 get_loss_tracking_rgb + autograd). */
 int32_t mgs_tracking_loss_onepass(const mgs_tracking_loss_args* args, int32_t* num_blocks_out, void* stream);
 
 

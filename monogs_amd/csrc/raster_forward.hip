@@ -1080,10 +1080,10 @@ __device__ __forceinline__ void blend_fwd(const KP& P, const KObjDepth& PD) {
   }
   if constexpr (OBJ) {
     // Tracking objective || Huber(opacity * mask * ((|a| + eps) * image + b - gt)) ||_p (p = 2 or 1), one pixel per lane:
-    // the per-sample arithmetic of k_track_loss_onepass (tracking.hip), channel by channel; d(loss)/d(image)
+    // the rows of objective_math.h (as track_loss_pass, tracking.hip), channel by channel; d(loss)/d(image)
     // WITHOUT the loss^(1-p) of the norm (k_pose_adam_update applies it to the pose gradient, which is linear in
     // it).  The wave's four sums become partial entry `item` (= 4 tile + quadrant).
-    float acc = 0.f, ga = 0.f, gb = 0.f, l1 = 0.f;
+    ObjSums s = {0.f, 0.f, 0.f, 0.f};
     const float a = P.obj.exposure_a[0];
     if (px_e < P.W && py_e < P.H) {
       const size_t HW = (size_t)P.W * P.H;
@@ -1091,50 +1091,40 @@ __device__ __forceinline__ void blend_fwd(const KP& P, const KObjDepth& PD) {
       const float gain = fabsf(a) + P.obj.exposure_eps, bias = P.obj.exposure_b[0];
       const float om = (1.f - T) * (P.obj.mask ? P.obj.mask[pix] : 1.f);
       const float im[3] = {C01.x + T * P.bg[0], C01.y + T * P.bg[1], C2D.x + T * P.bg[2]};
+      const float pn = P.obj.p1 ? 1.f : 2.f;
       float gt[3];
 #pragma unroll
       for (int c = 0; c < 3; c++) gt[c] = P.obj.gt[c * HW + pix];
 #pragma unroll
-      for (int c = 0; c < 3; c++) {
-        float dh;
-        float r = om * (gain * im[c] + bias - gt[c]);
-        if constexpr (DEPTH) r *= PD.w_rgb;            // alpha * rgb_pp, Huber after the weighting
-        l1 += fabsf(r);
-        const float h = huber(r, P.obj.huber_delta, dh);
-        float phi, gam;
-        norm_terms(h, P.obj.p1 ? 1.f : 2.f, phi, gam);
-        acc += phi;
-        float gr = gam * dh * om;
-        if constexpr (DEPTH) gr *= PD.w_rgb;
-        ga += gr * im[c];
-        gb += gr;
-        P.obj.grad_image[c * HW + pix] = gr * gain;
-      }
+      for (int c = 0; c < 3; c++)
+        P.obj.grad_image[c * HW + pix] =
+            colour_row(DEPTH, om, gain, bias, im[c], gt[c], PD.w_rgb, 1.f, P.obj.huber_delta, pn, s) * gain;
       if constexpr (DEPTH) {
-        // r_d = (1 - alpha) (depth dm - gt_depth dm), dm = (gt_depth > 0.01) & (opacity > 0.95): the rendered depth
-        // and opacity are the wave's own registers; the row does not touch the exposure sums
+        // depth_row of objective_math.h written out (a call changes this kernel's block order): the rendered depth and
+        // opacity are the wave's own registers
         const float gtd = PD.gt_depth[pix];
         const float dm = (gtd > PD.depth_thr && 1.f - T > PD.opa_thr) ? 1.f : 0.f;
         const float rd = PD.w_depth * (C2D.y * dm - gtd * dm);
         float dh, phi, gam;
-        l1 += fabsf(rd);
+        s.l1 += fabsf(rd);
         const float h = huber(rd, P.obj.huber_delta, dh);
-        norm_terms(h, P.obj.p1 ? 1.f : 2.f, phi, gam);
-        acc += phi;
+        norm_terms(h, pn, phi, gam);
+        s.phi += phi;
         PD.grad_depth[pix] = gam * dh * PD.w_depth * dm;
       }
     }
 #pragma unroll
     for (int off = 32; off > 0; off >>= 1) {
-      acc += __shfl_down(acc, off); ga += __shfl_down(ga, off); gb += __shfl_down(gb, off); l1 += __shfl_down(l1, off);
+      s.phi += __shfl_down(s.phi, off); s.da += __shfl_down(s.da, off); s.db += __shfl_down(s.db, off);
+      s.l1 += __shfl_down(s.l1, off);
     }
     if (lane == 0) {
       const size_t n = 4 * (size_t)P.T;
-      const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
-      P.obj.partial[item] = acc;
-      P.obj.partial[n + item] = ga * sgn;
-      P.obj.partial[2 * n + item] = gb;
-      P.obj.partial[3 * n + item] = l1;
+      const float sa = sgn(a);
+      P.obj.partial[item] = s.phi;
+      P.obj.partial[n + item] = s.da * sa;
+      P.obj.partial[2 * n + item] = s.db;
+      P.obj.partial[3 * n + item] = s.l1;
     }
   }
 }

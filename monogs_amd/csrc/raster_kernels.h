@@ -35,7 +35,7 @@ namespace mgs {
 // by value (kernarg segment -> SGPRs).
 // Tracking objective evaluated in the forward blend's epilogue (native first-order tracking iteration only:
 // mgs_tracking_iteration).  The quadrant wave that has just finished a pixel holds its colour and opacity in
-// registers; it forms the residual of tracking.hip's k_track_loss_onepass there, writes d(loss)/d(image) for the
+// registers; it forms the residual rows of objective_math.h there, writes d(loss)/d(image) for the
 // backward and leaves its four sums as ONE partial per quadrant wave - the loss launch between the forward and
 // the backward is gone.
 struct KObj {

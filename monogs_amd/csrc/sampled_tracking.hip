@@ -44,7 +44,7 @@ __device__ __forceinline__ float wsum(float v) {
   return v;
 }
 
-// residual rows of one pixel (the arithmetic of k_track_loss_onepass / k_track_loss_rgbd), their value sums and
+// residual rows of one pixel (objective_math.h: the rows of track_loss_pass), their value sums and
 // the UN-normalised upstream gradient: gr[c] = d(sum_c |h_c|^p / p)/d(image_c) / gain, gd = .../d depth
 struct SampPixel {
   float psi, l1, v, gr[3], gd;
@@ -56,29 +56,16 @@ __device__ __forceinline__ void samp_pixel(const KS& S, size_t p, float gain, fl
   const float opa = S.opacity[p];
   const float om = opa * (S.mask ? S.mask[p] : 1.f);
   const float wr = S.rgbd ? S.w_rgb : 1.f;
-  o.psi = 0.f; o.l1 = 0.f; o.gd = 0.f;
+  ObjSums s = {0.f, 0.f, 0.f, 0.f};       // (the exposure sums are not used: the backward forms them per sample)
+  o.gd = 0.f;
 #pragma unroll
   for (int c = 0; c < 3; c++) {
-    float dh, phi, gam;
-    const float r = S.rgbd ? om * (gain * S.image[c * HW + p] + bias - S.gt[c * HW + p]) * wr
-                           : om * (gain * S.image[c * HW + p] + bias - S.gt[c * HW + p]);
-    o.l1 += fabsf(r);
-    const float h = huber(r, S.huber_delta, dh);
-    norm_terms(h, pn, phi, gam);
-    o.psi += phi;
-    o.gr[c] = S.rgbd ? gam * dh * om * wr : gam * dh * om;
+    const float im = S.image[c * HW + p], gt = S.gt[c * HW + p];
+    o.gr[c] = colour_row(S.rgbd, om, gain, bias, im, gt, wr, 1.f, S.huber_delta, pn, s);
   }
-  if (S.rgbd) {
-    const float gtd = S.gt_depth[p];
-    const float dm = (gtd > S.depth_thr && opa > S.opa_thr) ? 1.f : 0.f;
-    const float rd = S.w_depth * (S.depth[p] * dm - gtd * dm);
-    float dh, phi, gam;
-    o.l1 += fabsf(rd);
-    const float h = huber(rd, S.huber_delta, dh);
-    norm_terms(h, pn, phi, gam);
-    o.psi += phi;
-    o.gd = gam * dh * S.w_depth * dm;
-  }
+  if (S.rgbd)
+    o.gd = depth_row(S.gt_depth[p], opa, S.depth[p], S.depth_thr, S.opa_thr, S.w_depth, S.huber_delta, pn, s);
+  o.psi = s.phi; o.l1 = s.l1;
   o.v = o.l1 + 1e-8f;
 }
 

@@ -68,7 +68,7 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
   // which is NOT the exact derivative of (|a| + eps) image + b: grad_image = |a| grad (no eps) and
   // grad_a = sum(grad image) (no sign(a)).  Followed to the letter here (pinned by tests/golden/map_update_ref.npz:
   // ae_*); the first-order path differentiates the same expression by autograd and keeps sign(a) and eps
-  // (k_track_loss_bwd / _onepass, the forward blend's objective epilogue).
+  // (colour_row of objective_math.h: track_loss_pass, the forward blend's objective epilogue).
   const float gain_bwd = fabsf(A.exposure_a[0]);
   const float gain = gain_bwd + A.exposure_eps, bias = A.exposure_b[0];
   const size_t HW = (size_t)A.num_pixels;
@@ -96,7 +96,7 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
 #pragma unroll
     for (int c = 0; c < 3; c++) {
       const float im = A.image[c * HW + p];
-      float r = om * (gain * im + bias - A.gt[c * HW + p]);
+      float r = colour_residual(om, gain, bias, im, A.gt[c * HW + p]);
       if constexpr (DEPTH) r *= D->w_rgb;
       l1 += fabsf(r);
       float dh;
@@ -109,8 +109,9 @@ __device__ __forceinline__ void sketch_residual_block(const mgs_sketch_residual_
     }
     if constexpr (DEPTH) {
       const float gtd = D->gt_depth[p];
+      // (dm as in depth_row of objective_math.h; written out so that the opacity is re-read behind the first test)
       const float dm = (gtd > D->depth_threshold && A.opacity[p] > D->opacity_threshold) ? 1.f : 0.f;
-      const float rd = D->w_depth * (D->depth[p] * dm - gtd * dm);
+      const float rd = depth_residual(D->depth[p], gtd, dm, D->w_depth);
       l1 += fabsf(rd);
       float dh;
       hs += huber(rd, A.huber_delta, dh);

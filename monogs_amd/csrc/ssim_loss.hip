@@ -301,7 +301,7 @@ __global__ __launch_bounds__(ssim::kThreads) void k_ssim_loss(mgs_ssim_loss_args
   const int n = gridDim.x * gridDim.y * gridDim.z;
   const int blk = (blockIdx.z * gridDim.y + blockIdx.y) * gridDim.x + blockIdx.x;
   __shared__ int s_last;
-  if (tid == 0) {   // write-through stores, then the ticket (as k_map_loss_fused)
+  if (tid == 0) {   // write-through stores, then the ticket (as k_map_loss, tracking.hip)
     __hip_atomic_store(&A.partial[blk], tl, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(&A.partial[n + blk], ts, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __threadfence();

@@ -5,11 +5,13 @@
 //    (cam_rot_delta, cam_trans_delta, exposure_a, exposure_b; utils/slam_frontend.py:364-392)
 //    followed by update_pose (utils/pose_utils.py:88-98): T <- Exp([rho; theta]) T, deltas
 //    zeroed, convergence flag.  One thread; replaces ~60 launches and two host syncs.
-//  * k_track_loss_fwd / k_track_loss_bwd: monocular tracking objective
-//    || Huber( opacity * mask * ((|a|+eps) * image + b - gt) ) ||_2
-//    (utils/slam_utils.py:188-205 + :58-75 + slam_frontend.py:596-598), forward and
-//    backward (d/d image, d/d a, d/d b), HBM-bound streaming kernels.
+//  * track_loss_pass: the tracking objective
+//    || Huber( opacity * mask * ((|a|+eps) * image + b - gt) ) ||_p   (RGB-D: with the depth row stacked on)
+//    (utils/slam_utils.py:188-205 + :58-75 + slam_frontend.py:596-600), value and / or gradients
+//    (d/d image, d/d a, d/d b), HBM-bound streaming kernels; k_map_loss: the same for the mapping objective.
 #include <hip/hip_runtime.h>
+
+#include <initializer_list>
 
 #include "../../include/monogs_raster.h"
 #include "launch.h"
@@ -259,120 +261,31 @@ __device__ __forceinline__ float block_sum(float v, float* s_red) {
   return t;
 }
 
-// partial[b] = sum over the block's pixels of |h|^p (3 channels)
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_fwd(mgs_tracking_loss_args A) {
-  __shared__ float s_red[kLossBlock / 64];
-  const float gain = fabsf(A.exposure_a[0]) + A.exposure_eps, bias = A.exposure_b[0];
-  const float pn = norm_p(A.pnorm);
-  const size_t HW = (size_t)A.num_pixels;
-  float acc = 0.f;
-  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-    const float om = A.opacity[p] * (A.mask ? A.mask[p] : 1.f);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      float dh, phi, gam;
-      const float h = huber(om * (gain * A.image[c * HW + p] + bias - A.gt[c * HW + p]), A.huber_delta, dh);
-      norm_terms(h, pn, phi, gam);
-      acc += phi;
-    }
-  }
-  const float t = block_sum(acc, s_red);
-  if (threadIdx.x == 0) A.partial[blockIdx.x] = t;
-}
-
-// loss = (sum partial)^(1/p); scalars[0] = loss, scalars[1] = loss^(1-p) (1/loss for p = 2; 0 if loss == 0)
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_finish(mgs_tracking_loss_args A, int nblk) {
-  __shared__ float s_red[kLossBlock / 64];
-  float acc = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += kLossBlock) acc += A.partial[i];
-  const float t = block_sum(acc, s_red);
-  if (threadIdx.x == 0) {
-    float l, sc;
-    norm_finish(t, norm_p(A.pnorm), l, sc);
-    A.scalars[0] = l;
-    A.scalars[1] = sc;
-  }
-}
-
-// grad_image = gout/loss * h * h' * om * gain ; partial sums for d/da, d/db
-// nfwd > 0 (fused form, mgs_tracking_iteration): the forward's nfwd block sums are added up
-// here by every workgroup (no k_track_loss_finish launch) and the exposure partials go
-// BEHIND them in `partial` (summed by k_pose_adam_update, no k_track_loss_bwd_finish launch).
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_bwd(mgs_tracking_loss_args A, int nfwd) {
+// The tracking objective as one streaming pass (HBM-bound), its rows those of objective_math.h:
+//   VALUE  the block sums of |h|^p (and, with GRAD, of |r| before Huber)
+//   GRAD   d/d image and the block sums of d/da, d/db.  Alone (the backward of an earlier VALUE pass) they carry
+//          k = grad_out * loss^(1-p), loss^(1-p) = scalars[1] of that pass; together with VALUE they are
+//          UN-normalised (k = 1) and the consumer of the sums applies the factor (k_track_loss_finish, or
+//          k_pose_adam_update: loss_norm_mode)
+//   DEPTH  RGB-D (mgs_tracking_depth_args): the three colour rows weighted by w_rgb, then the depth row, per pixel in
+//          that order (as the epilogue of k_blend_fwd_rgbd); d/d depth (un-normalised) into D.grad_depth
+//   VEC    four consecutive pixels per thread and trip through 16-B loads / stores (as k_map_loss<true, true, true>)
+// partial = [n] sum |h|^p | [n] d/da | [n] d/db | [n] sum |r|, n = gridDim.x; a slot its pass does not form is left alone.
+template <bool VALUE, bool GRAD, bool DEPTH, bool VEC>
+__device__ __forceinline__ void track_loss_pass(const mgs_tracking_loss_args& A, const mgs_tracking_depth_args& D) {
+  static_assert(VALUE || GRAD, "nothing to compute");
+  static_assert(!VEC || (VALUE && GRAD && !DEPTH), "the vector path exists for the one-pass monocular form only");
   __shared__ float s_red[kLossBlock / 64];
   const float a = A.exposure_a[0];
   const float gain = fabsf(a) + A.exposure_eps, bias = A.exposure_b[0];
-  const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
-  const float pn = norm_p(A.pnorm);
-  float inv_loss = 0.f;      // loss^(1-p), the factor of the norm's derivative
-  if (nfwd > 0) {
-    float acc = 0.f;
-    for (int i = threadIdx.x; i < nfwd; i += kLossBlock) acc += A.partial[i];
-    float l;
-    norm_finish(block_sum(acc, s_red), pn, l, inv_loss);
-    if (blockIdx.x == 0 && threadIdx.x == 0) { A.scalars[0] = l; A.scalars[1] = inv_loss; }
-    __syncthreads();
-  } else {
-    inv_loss = A.scalars[1];
-  }
-  const float k = A.grad_out[0] * inv_loss;
-  const size_t HW = (size_t)A.num_pixels;
-  float ga = 0.f, gb = 0.f;
-  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-    const float om = A.opacity[p] * (A.mask ? A.mask[p] : 1.f);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float im = A.image[c * HW + p];
-      float dh, phi, gam;
-      const float h = huber(om * (gain * im + bias - A.gt[c * HW + p]), A.huber_delta, dh);
-      norm_terms(h, pn, phi, gam);
-      const float gr = k * gam * dh * om;     // dL/d(residual before opacity) * om
-      A.grad_image[c * HW + p] = gr * gain;
-      ga += gr * im;
-      gb += gr;
-    }
-  }
-  const float ta = block_sum(ga, s_red);
-  const float tb = block_sum(gb, s_red);
-  if (threadIdx.x == 0) {
-    A.partial[nfwd + blockIdx.x] = ta * sgn;
-    A.partial[nfwd + gridDim.x + blockIdx.x] = tb;
-  }
-}
-
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_bwd_finish(mgs_tracking_loss_args A, int nblk) {
-  __shared__ float s_red[kLossBlock / 64];
-  float x = 0.f, y = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += kLossBlock) { x += A.partial[i]; y += A.partial[nblk + i]; }
-  const float ta = block_sum(x, s_red);
-  const float tb = block_sum(y, s_red);
-  if (threadIdx.x == 0) { A.grad_a[0] = ta; A.grad_b[0] = tb; }
-}
-
-// One pass (mgs_tracking_loss_onepass): block sums of |h|^p, the image gradient and the exposure
-// partials WITHOUT the loss^(1-p) factor of the norm's derivative (1 / loss for p = 2); k_pose_adam_update applies it
-// (loss_norm_mode).  partial = [n] sum |h|^p | [n] d/da | [n] d/db | [n] sum |r| (before Huber).
-// VEC: four consecutive pixels per thread and trip through 16-B loads / stores (as k_map_loss_fused<true>).
-template <bool VEC>
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_onepass(mgs_tracking_loss_args A) {
-  __shared__ float s_red[kLossBlock / 64];
-  const float a = A.exposure_a[0];
-  const float gain = fabsf(a) + A.exposure_eps, bias = A.exposure_b[0];
-  const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
+  const float sa = sgn(a);
   const size_t HW = (size_t)A.num_pixels;
   const float pn = norm_p(A.pnorm);
-  float acc = 0.f, ga = 0.f, gb = 0.f, l1 = 0.f;
+  float k = 1.f;
+  if constexpr (GRAD && !VALUE) k = A.grad_out[0] * A.scalars[1];
+  ObjSums s = {0.f, 0.f, 0.f, 0.f};
   auto sample = [&](float om, float im, float gt) {      // one colour sample: sums + d/d image
-    float dh, phi, gam;
-    const float r = om * (gain * im + bias - gt);
-    l1 += fabsf(r);
-    const float h = huber(r, A.huber_delta, dh);
-    norm_terms(h, pn, phi, gam);
-    acc += phi;
-    const float gr = gam * dh * om;
-    ga += gr * im;
-    gb += gr;
-    return gr * gain;
+    return colour_row(DEPTH, om, gain, bias, im, gt, D.w_rgb, k, A.huber_delta, pn, s) * gain;
   };
   if constexpr (VEC) {
     const size_t Q = HW / 4;
@@ -402,90 +315,64 @@ __global__ __launch_bounds__(kLossBlock) void k_track_loss_onepass(mgs_tracking_
     }
   } else {
     for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-      const float om = A.opacity[p] * (A.mask ? A.mask[p] : 1.f);
+      const float opa = A.opacity[p];
+      const float om = opa * (A.mask ? A.mask[p] : 1.f);
 #pragma unroll
-      for (int c = 0; c < 3; c++) A.grad_image[c * HW + p] = sample(om, A.image[c * HW + p], A.gt[c * HW + p]);
+      for (int c = 0; c < 3; c++) {
+        const float g = sample(om, A.image[c * HW + p], A.gt[c * HW + p]);
+        if constexpr (GRAD) A.grad_image[c * HW + p] = g;
+      }
+      if constexpr (DEPTH)
+        D.grad_depth[p] = depth_row(D.gt_depth[p], opa, D.depth[p], D.depth_threshold, D.opacity_threshold, D.w_depth,
+                                    A.huber_delta, pn, s);
     }
   }
-  const float t = block_sum(acc, s_red);
-  const float ta = block_sum(ga, s_red);
-  const float tb = block_sum(gb, s_red);
-  const float tl = block_sum(l1, s_red);
+  float t = 0.f, ta = 0.f, tb = 0.f, tl = 0.f;
+  if constexpr (VALUE) t = block_sum(s.phi, s_red);
+  if constexpr (GRAD) { ta = block_sum(s.da, s_red); tb = block_sum(s.db, s_red); }
+  if constexpr (VALUE && GRAD) tl = block_sum(s.l1, s_red);
   if (threadIdx.x == 0) {
-    A.partial[blockIdx.x] = t;
-    A.partial[gridDim.x + blockIdx.x] = ta * sgn;
-    A.partial[2 * gridDim.x + blockIdx.x] = tb;
-    A.partial[3 * gridDim.x + blockIdx.x] = tl;
+    if constexpr (VALUE) A.partial[blockIdx.x] = t;
+    if constexpr (GRAD) {
+      A.partial[gridDim.x + blockIdx.x] = ta * sa;
+      A.partial[2 * gridDim.x + blockIdx.x] = tb;
+    }
+    if constexpr (VALUE && GRAD) A.partial[3 * gridDim.x + blockIdx.x] = tl;
   }
 }
 
-// RGB-D form of k_track_loss_onepass (mgs_tracking_loss_rgbd_fused): the three colour rows weighted by w_rgb and the
-// depth row r_d = w_depth (depth dm - gt_depth dm) per pixel, in that order (the arithmetic of k_blend_fwd<true, true>'s
-// epilogue).  Same partial layout; d/d depth (un-normalised) into D.grad_depth.
+template <bool VALUE, bool GRAD, bool VEC>
+__global__ __launch_bounds__(kLossBlock) void k_track_loss(mgs_tracking_loss_args A) {
+  track_loss_pass<VALUE, GRAD, false, VEC>(A, mgs_tracking_depth_args{});
+}
+
 __global__ __launch_bounds__(kLossBlock) void k_track_loss_rgbd(mgs_tracking_loss_args A, mgs_tracking_depth_args D) {
-  __shared__ float s_red[kLossBlock / 64];
-  const float a = A.exposure_a[0];
-  const float gain = fabsf(a) + A.exposure_eps, bias = A.exposure_b[0];
-  const float sgn = a > 0.f ? 1.f : (a < 0.f ? -1.f : 0.f);
-  const size_t HW = (size_t)A.num_pixels;
-  const float pn = norm_p(A.pnorm);
-  float acc = 0.f, ga = 0.f, gb = 0.f, l1 = 0.f;
-  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-    const float opa = A.opacity[p];
-    const float om = opa * (A.mask ? A.mask[p] : 1.f);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float im = A.image[c * HW + p];
-      float dh, phi, gam;
-      const float r = om * (gain * im + bias - A.gt[c * HW + p]) * D.w_rgb;
-      l1 += fabsf(r);
-      const float h = huber(r, A.huber_delta, dh);
-      norm_terms(h, pn, phi, gam);
-      acc += phi;
-      const float gr = gam * dh * om * D.w_rgb;
-      ga += gr * im;
-      gb += gr;
-      A.grad_image[c * HW + p] = gr * gain;
-    }
-    const float gtd = D.gt_depth[p];
-    const float dm = (gtd > D.depth_threshold && opa > D.opacity_threshold) ? 1.f : 0.f;
-    const float rd = D.w_depth * (D.depth[p] * dm - gtd * dm);
-    float dh, phi, gam;
-    l1 += fabsf(rd);
-    const float h = huber(rd, A.huber_delta, dh);
-    norm_terms(h, pn, phi, gam);
-    acc += phi;
-    D.grad_depth[p] = gam * dh * D.w_depth * dm;
-  }
-  const float t = block_sum(acc, s_red);
-  const float ta = block_sum(ga, s_red);
-  const float tb = block_sum(gb, s_red);
-  const float tl = block_sum(l1, s_red);
-  if (threadIdx.x == 0) {
-    A.partial[blockIdx.x] = t;
-    A.partial[gridDim.x + blockIdx.x] = ta * sgn;
-    A.partial[2 * gridDim.x + blockIdx.x] = tb;
-    A.partial[3 * gridDim.x + blockIdx.x] = tl;
-  }
+  track_loss_pass<true, true, true, false>(A, D);
 }
 
-// scalars[0] = loss, scalars[1] = loss^(1-p); grad_a / grad_b = the exposure sums times loss^(1-p) (when not NULL)
-__global__ __launch_bounds__(kLossBlock) void k_track_loss_rgbd_finish(mgs_tracking_loss_args A, int nblk) {
+// Sums of the block partials in index order.  value: scalars[0] = loss = (sum |h|^p)^(1/p), scalars[1] = loss^(1-p)
+// (1 / loss for p = 2; 0 if loss == 0).  grads: grad_a / grad_b (when not NULL) = the exposure sums, times the
+// loss^(1-p) of this launch when it forms the value too (the partials of a gradient-only pass carry theirs already).
+__global__ __launch_bounds__(kLossBlock) void k_track_loss_finish(mgs_tracking_loss_args A, int nblk, int value, int grads) {
   __shared__ float s_red[kLossBlock / 64];
   float s = 0.f, x = 0.f, y = 0.f;
   for (int i = threadIdx.x; i < nblk; i += kLossBlock) {
-    s += A.partial[i]; x += A.partial[nblk + i]; y += A.partial[2 * nblk + i];
+    if (value) s += A.partial[i];
+    if (grads) { x += A.partial[nblk + i]; y += A.partial[2 * nblk + i]; }
   }
   const float ts = block_sum(s, s_red);
   const float tx = block_sum(x, s_red);
   const float ty = block_sum(y, s_red);
   if (threadIdx.x == 0) {
-    float l, sc;
-    norm_finish(ts, norm_p(A.pnorm), l, sc);
-    A.scalars[0] = l;
-    A.scalars[1] = sc;
-    if (A.grad_a) A.grad_a[0] = tx * sc;
-    if (A.grad_b) A.grad_b[0] = ty * sc;
+    float sc = 1.f;
+    if (value) {
+      float l;
+      norm_finish(ts, norm_p(A.pnorm), l, sc);
+      A.scalars[0] = l;
+      A.scalars[1] = sc;
+    }
+    if (grads && A.grad_a) A.grad_a[0] = tx * sc;
+    if (grads && A.grad_b) A.grad_b[0] = ty * sc;
   }
 }
 
@@ -670,141 +557,69 @@ __global__ __launch_bounds__(128) void k_lm_solve_normal(mgs_lm_step_args A, con
 //   loss = w_rgb * mean_{3HW} | m * ((|a|+eps) img + b - gt) |  +  w_depth * mean_{HW} | dm * (depth - gt_depth) |
 // with m = rgb_pixel_mask_mapping and dm = gt_depth > 0.01 (RGB-D only; w_depth = 0 for
 // monocular).  apply_exposure = 0 reproduces `initialization=True` (image used as is).
-// One streaming pass for the value, one for the gradients.
-__global__ __launch_bounds__(kLossBlock) void k_map_loss_fwd(mgs_mapping_loss_args A, int fused_finish) {
-  __shared__ float s_red[kLossBlock / 64];
-  const float gain = A.apply_exposure ? fabsf(A.exposure_a[0]) + A.exposure_eps : 1.f;
-  const float bias = A.apply_exposure ? A.exposure_b[0] : 0.f;
-  const size_t HW = (size_t)A.num_pixels;
-  float sc = 0.f, sd = 0.f;
-  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-    const float m = A.mask ? A.mask[p] : 1.f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) sc += fabsf(m * (gain * A.image[c * HW + p] + bias - A.gt[c * HW + p]));
-    if (A.w_depth != 0.f) {
-      const float gdp = A.gt_depth[p];
-      const float dm = (A.depth_mask_threshold < 0.f || gdp > A.depth_mask_threshold) ? 1.f : 0.f;
-      sd += fabsf(dm * (A.depth[p] - gdp));
+// One streaming pass, for the value (VALUE), for the gradients (GRAD) or for both: the L1 gradient does not depend on
+// the loss value, so nothing has to wait for a reduction.  Block partials [4][n]: sum |colour residual|,
+// sum |depth residual| (VALUE), d/da, d/db (GRAD); a slot the pass does not form is left alone.
+
+// Fixed-order sum of the block partials and what is made of it: loss (VALUE), grad_a / grad_b (GRAD), each when not
+// NULL.  ticket: called by every workgroup of the streaming pass, behind its partial stores; the one that arrives
+// last does the work (saves the dependent finish launch).  Otherwise: the body of the finish launch.
+template <bool VALUE, bool GRAD>
+__device__ __forceinline__ void map_loss_finish(const mgs_mapping_loss_args& A, int n, bool ticket, float* s_red) {
+  if (ticket) {
+    // Fence-free hand-off as in k_bin_colsum (MI355X_MICROARCH.md, "Hand-offs measured with sc1
+    // loads"): the partials were stored write-through, the storing lane drains them
+    // (s_waitcnt) and takes an agent-scope ticket; the last arriver reads with sc1 loads.  A full
+    // __threadfence() here costs an L2 write-back per workgroup: 7.7 -> 17 us for this kernel.
+    // The ticket (the int behind the 4 n partials) is zero on entry and is reset here, so the same
+    // scratch serves the next call.
+    __shared__ int s_last;
+    if (threadIdx.x == 0) {
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      int* ticket = reinterpret_cast<int*>(A.partial + 4 * n);
+      s_last = atomicAdd(ticket, 1) == n - 1;
+      if (s_last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
+    __syncthreads();
+    if (!s_last) return;
   }
-  const float tc = block_sum(sc, s_red);
-  const float td = block_sum(sd, s_red);
-  if (threadIdx.x == 0) {   // write-through (sc1) stores: visible to the last workgroup's sc1 loads without a fence
-    __hip_atomic_store(&A.partial[blockIdx.x], tc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&A.partial[gridDim.x + blockIdx.x], td, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!fused_finish) return;
-  // The workgroup that finishes last sums the block partials (saves the dependent finish launch).
-  // Fence-free hand-off as in k_bin_colsum (MI355X_MICROARCH.md, "Hand-offs measured with sc1
-  // loads"): the two partials were stored write-through, the storing lane drains them
-  // (s_waitcnt) and takes an agent-scope ticket; the last arriver reads with sc1 loads.  A full
-  // __threadfence() here costs an L2 write-back per workgroup: 7.7 -> 17 us for this kernel.
-  // The ticket (the int behind the 2 n partials) is zero on entry and is reset here, so the same
-  // scratch serves the next call.
-  __shared__ int s_last;
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int* ticket = reinterpret_cast<int*>(A.partial + 2 * gridDim.x);
-    s_last = atomicAdd(ticket, 1) == (int)gridDim.x - 1;
-    if (s_last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  const int nblk = gridDim.x;
-  float x = 0.f, y = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += kLossBlock) {
-    x += __hip_atomic_load(&A.partial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    y += __hip_atomic_load(&A.partial[nblk + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  const float sumc = block_sum(x, s_red);
-  const float sumd = block_sum(y, s_red);
+  constexpr int c0 = VALUE ? 0 : 2, c1 = GRAD ? 4 : 2;
+  float acc[4] = {0.f, 0.f, 0.f, 0.f};
+  for (int i = threadIdx.x; i < n; i += kLossBlock)
+#pragma unroll
+    for (int c = c0; c < c1; c++) acc[c] += __hip_atomic_load(&A.partial[c * n + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  float tot[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+  for (int c = c0; c < c1; c++) tot[c] = block_sum(acc[c], s_red);
   if (threadIdx.x == 0) {
     const float hw = (float)A.num_pixels;
-    A.loss[0] = A.w_rgb * sumc / (3.f * hw) + A.w_depth * sumd / hw;
+    if (VALUE && A.loss) A.loss[0] = A.w_rgb * tot[0] / (3.f * hw) + A.w_depth * tot[1] / hw;
+    if (GRAD && A.grad_a) A.grad_a[0] = tot[2];
+    if (GRAD && A.grad_b) A.grad_b[0] = tot[3];
   }
 }
 
-__global__ __launch_bounds__(kLossBlock) void k_map_loss_finish(mgs_mapping_loss_args A, int nblk) {
-  __shared__ float s_red[kLossBlock / 64];
-  float x = 0.f, y = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += kLossBlock) { x += A.partial[i]; y += A.partial[nblk + i]; }
-  const float tc = block_sum(x, s_red);
-  const float td = block_sum(y, s_red);
-  if (threadIdx.x == 0) {
-    const float hw = (float)A.num_pixels;
-    A.loss[0] = A.w_rgb * tc / (3.f * hw) + A.w_depth * td / hw;
-  }
-}
-
-__device__ __forceinline__ float sgn(float v) { return v > 0.f ? 1.f : (v < 0.f ? -1.f : 0.f); }
-
-__global__ __launch_bounds__(kLossBlock) void k_map_loss_bwd(mgs_mapping_loss_args A) {
-  __shared__ float s_red[kLossBlock / 64];
-  const float a = A.apply_exposure ? A.exposure_a[0] : 1.f;
-  const float gain = A.apply_exposure ? fabsf(a) + A.exposure_eps : 1.f;
-  const float bias = A.apply_exposure ? A.exposure_b[0] : 0.f;
-  const size_t HW = (size_t)A.num_pixels;
-  const float hw = (float)A.num_pixels;
-  const float kc = A.grad_out[0] * A.w_rgb / (3.f * hw), kd = A.grad_out[0] * A.w_depth / hw;
-  float ga = 0.f, gb = 0.f;
-  for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
-    const float m = A.mask ? A.mask[p] : 1.f;
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const float im = A.image[c * HW + p];
-      const float g = kc * m * sgn(m * (gain * im + bias - A.gt[c * HW + p]));
-      A.grad_image[c * HW + p] = g * gain;
-      ga += g * im;
-      gb += g;
-    }
-    if (A.grad_depth) {
-      float g = 0.f;
-      if (A.w_depth != 0.f) {
-        const float gdp = A.gt_depth[p];
-        const float dm = (A.depth_mask_threshold < 0.f || gdp > A.depth_mask_threshold) ? 1.f : 0.f;
-        g = kd * dm * sgn(dm * (A.depth[p] - gdp));
-      }
-      A.grad_depth[p] = g;
-    }
-  }
-  const float ta = block_sum(ga, s_red);
-  const float tb = block_sum(gb, s_red);
-  if (threadIdx.x == 0) {
-    A.partial[blockIdx.x] = ta * sgn(a);
-    A.partial[gridDim.x + blockIdx.x] = tb;
-  }
-}
-
-__global__ __launch_bounds__(kLossBlock) void k_map_loss_bwd_finish(mgs_mapping_loss_args A, int nblk) {
-  __shared__ float s_red[kLossBlock / 64];
-  float x = 0.f, y = 0.f;
-  for (int i = threadIdx.x; i < nblk; i += kLossBlock) { x += A.partial[i]; y += A.partial[nblk + i]; }
-  const float ta = block_sum(x, s_red);
-  const float tb = block_sum(y, s_red);
-  if (threadIdx.x == 0) {
-    if (A.grad_a) A.grad_a[0] = A.apply_exposure ? ta : 0.f;
-    if (A.grad_b) A.grad_b[0] = A.apply_exposure ? tb : 0.f;
-  }
-}
-
-// Value AND gradients of the mapping objective in ONE pass (mgs_mapping_view_iteration): the L1
-// gradient does not depend on the loss value, so nothing has to wait for a reduction.  Block
-// partials [4][n]: sum |colour residual|, sum |depth residual|, d/da, d/db; their consumer
-// (k_pose_adam_update) sums them in a fixed order.  The upstream gradient is 1 unless
-// A.grad_out is given.
+// The upstream gradient is 1 unless A.grad_out is given.  A.partial_ticket_ready (with VALUE): the last workgroup
+// finishes the sums.
 // VEC: four consecutive pixels per thread and trip through 16-B loads / stores (num_pixels % 4 == 0 and
 // 16-B aligned planes, checked on the host): at 640x480 every thread makes ONE trip with ten independent
 // 16-B loads in flight instead of 2-3 trips of dword loads, and 300 workgroups leave 300 partials.
-template <bool VEC>
-__global__ __launch_bounds__(kLossBlock) void k_map_loss_fused(mgs_mapping_loss_args A) {
+template <bool VALUE, bool GRAD, bool VEC>
+__global__ __launch_bounds__(kLossBlock) void k_map_loss(mgs_mapping_loss_args A) {
+  static_assert(!VEC || (VALUE && GRAD), "the vector path exists for the one-pass form only");
   __shared__ float s_red[kLossBlock / 64];
   const float a = A.apply_exposure ? A.exposure_a[0] : 1.f;
   const float gain = A.apply_exposure ? fabsf(a) + A.exposure_eps : 1.f;
   const float bias = A.apply_exposure ? A.exposure_b[0] : 0.f;
   const size_t HW = (size_t)A.num_pixels;
   const float hw = (float)A.num_pixels;
-  const float go = A.grad_out ? A.grad_out[0] : 1.f;
-  const float kc = go * A.w_rgb / (3.f * hw), kd = go * A.w_depth / hw;
+  float kc = 0.f, kd = 0.f;
+  if constexpr (GRAD) {
+    // (the gradient-only pass requires grad_out: an unconditional load joins the other scalar loads instead of
+    // waiting behind a test of the pointer)
+    const float go = (!VALUE || A.grad_out) ? A.grad_out[0] : 1.f;
+    kc = go * A.w_rgb / (3.f * hw); kd = go * A.w_depth / hw;
+  }
   float sc = 0.f, sd = 0.f, ga = 0.f, gb = 0.f;
   // one colour sample / one depth sample: sums + gradient
   auto colour = [&](float m, float im, float gt) {
@@ -860,50 +675,44 @@ __global__ __launch_bounds__(kLossBlock) void k_map_loss_fused(mgs_mapping_loss_
     for (size_t p = (size_t)blockIdx.x * kLossBlock + threadIdx.x; p < HW; p += (size_t)gridDim.x * kLossBlock) {
       const float m = A.mask ? A.mask[p] : 1.f;
 #pragma unroll
-      for (int c = 0; c < 3; c++) A.grad_image[c * HW + p] = colour(m, A.image[c * HW + p], A.gt[c * HW + p]);
-      if (A.w_depth != 0.f) {
-        const float g = depth(A.depth[p], A.gt_depth[p]);
+      for (int c = 0; c < 3; c++) {
+        const float g = colour(m, A.image[c * HW + p], A.gt[c * HW + p]);
+        if constexpr (GRAD) A.grad_image[c * HW + p] = g;
+      }
+      float g = 0.f;
+      if (A.w_depth != 0.f) g = depth(A.depth[p], A.gt_depth[p]);
+      if constexpr (GRAD)
         if (A.grad_depth) A.grad_depth[p] = g;
-      } else if (A.grad_depth) {
-        A.grad_depth[p] = 0.f;
+    }
+  }
+  float tc = 0.f, td = 0.f, ta = 0.f, tb = 0.f;
+  if constexpr (VALUE) { tc = block_sum(sc, s_red); td = block_sum(sd, s_red); }
+  if constexpr (GRAD) { ta = block_sum(ga, s_red); tb = block_sum(gb, s_red); }
+  const int n = gridDim.x;
+  if (threadIdx.x == 0) {   // write-through (sc1) stores: visible to the last workgroup's sc1 loads without a fence
+    if constexpr (VALUE) {
+      __hip_atomic_store(&A.partial[blockIdx.x], tc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __hip_atomic_store(&A.partial[n + blockIdx.x], td, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if constexpr (GRAD) {
+      const float pa = A.apply_exposure ? ta * sgn(a) : 0.f, pb = A.apply_exposure ? tb : 0.f;
+      if constexpr (VALUE) {
+        __hip_atomic_store(&A.partial[2 * n + blockIdx.x], pa, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        __hip_atomic_store(&A.partial[3 * n + blockIdx.x], pb, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {      // no hand-off inside a gradient-only launch: plain stores (write-through ones cost it 0.3 us)
+        A.partial[2 * n + blockIdx.x] = pa;
+        A.partial[3 * n + blockIdx.x] = pb;
       }
     }
   }
-  const float tc = block_sum(sc, s_red);
-  const float td = block_sum(sd, s_red);
-  const float ta = block_sum(ga, s_red);
-  const float tb = block_sum(gb, s_red);
-  const int n = gridDim.x;
-  if (threadIdx.x == 0) {   // write-through stores: see the hand-off below
-    __hip_atomic_store(&A.partial[blockIdx.x], tc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&A.partial[n + blockIdx.x], td, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&A.partial[2 * n + blockIdx.x], A.apply_exposure ? ta * sgn(a) : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(&A.partial[3 * n + blockIdx.x], A.apply_exposure ? tb : 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  if (!A.partial_ticket_ready) return;
-  // optional finish by the workgroup that arrives last (fence-free hand-off as in k_map_loss_fwd; the
-  // ticket is the int behind the 4 n partials, zero on entry, reset here): loss and exposure gradients
-  __shared__ int s_last;
-  if (threadIdx.x == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    int* ticket = reinterpret_cast<int*>(A.partial + 4 * n);
-    s_last = atomicAdd(ticket, 1) == n - 1;
-    if (s_last) __hip_atomic_store(ticket, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-  __syncthreads();
-  if (!s_last) return;
-  float acc[4] = {0.f, 0.f, 0.f, 0.f};
-  for (int i = threadIdx.x; i < n; i += kLossBlock)
-#pragma unroll
-    for (int c = 0; c < 4; c++) acc[c] += __hip_atomic_load(&A.partial[c * n + i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float tot[4];
-#pragma unroll
-  for (int c = 0; c < 4; c++) tot[c] = block_sum(acc[c], s_red);
-  if (threadIdx.x == 0) {
-    if (A.loss) A.loss[0] = A.w_rgb * tot[0] / (3.f * hw) + A.w_depth * tot[1] / hw;
-    if (A.grad_a) A.grad_a[0] = tot[2];
-    if (A.grad_b) A.grad_b[0] = tot[3];
-  }
+  if constexpr (VALUE)      // (the gradient-only pass has no ticket form: mgs_mapping_loss_backward finishes in a second launch)
+    if (A.partial_ticket_ready) map_loss_finish<VALUE, GRAD>(A, n, true, s_red);
+}
+
+template <bool VALUE, bool GRAD>
+__global__ __launch_bounds__(kLossBlock) void k_map_loss_finish(mgs_mapping_loss_args A, int nblk) {
+  __shared__ float s_red[kLossBlock / 64];
+  map_loss_finish<VALUE, GRAD>(A, nblk, false, s_red);
 }
 
 
@@ -969,28 +778,37 @@ int32_t mgs_pose_adam_step(const mgs_pose_adam_args* a, void* stream) {
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
+// (a->loss is optional in mgs_mapping_loss_fused: the other two entries check it themselves)
 static bool map_args_ok(const mgs_mapping_loss_args* a) {
-  if (!a || !a->image || !a->gt || !a->partial || !a->loss || a->num_pixels < 1) return false;
+  if (!a || !a->image || !a->gt || !a->partial || a->num_pixels < 1) return false;
   if (a->apply_exposure && (!a->exposure_a || !a->exposure_b)) return false;
   if (a->w_depth != 0.f && (!a->depth || !a->gt_depth)) return false;
   return true;
 }
 
+// The vector path of the one-pass kernels: whole float4s, every plane (NULL: absent) 16-B aligned
+static bool vec_ok(int64_t num_pixels, std::initializer_list<const void*> planes) {
+  if (num_pixels % 4 != 0) return false;
+  for (const void* p : planes)
+    if (reinterpret_cast<uintptr_t>(p) & 15) return false;
+  return true;
+}
+
 int32_t mgs_mapping_loss_forward(const mgs_mapping_loss_args* a, void* stream) {
-  if (!map_args_ok(a)) return MGS_ERR_BAD_ARGUMENT;
+  if (!map_args_ok(a) || !a->loss) return MGS_ERR_BAD_ARGUMENT;
   const int nb = loss_blocks(a->num_pixels);
-  launch("map_loss_fwd", k_map_loss_fwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a, a->partial_ticket_ready ? 1 : 0);
+  launch("map_loss_fwd", k_map_loss<true, false, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   if (!a->partial_ticket_ready)
-    launch("map_loss_finish", k_map_loss_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
+    launch("map_loss_finish", k_map_loss_finish<true, false>, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 int32_t mgs_mapping_loss_backward(const mgs_mapping_loss_args* a, void* stream) {
-  if (!map_args_ok(a) || !a->grad_out || !a->grad_image) return MGS_ERR_BAD_ARGUMENT;
+  if (!map_args_ok(a) || !a->loss || !a->grad_out || !a->grad_image) return MGS_ERR_BAD_ARGUMENT;
   const int nb = loss_blocks(a->num_pixels);
-  launch("map_loss_bwd", k_map_loss_bwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+  launch("map_loss_bwd", k_map_loss<false, true, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   if (a->grad_a || a->grad_b)   // exposure gradients are the only consumers of the partial sums
-    launch("map_loss_bwd_fin", k_map_loss_bwd_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
+    launch("map_loss_bwd_fin", k_map_loss_finish<false, true>, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
@@ -998,18 +816,14 @@ int32_t mgs_mapping_loss_partial_count(int64_t num_pixels) { return 4 * loss_blo
 
 // Single-pass form used by mgs_mapping_view_iteration; partial = [4][*nblk_out].
 int32_t mgs_mapping_loss_fused(const mgs_mapping_loss_args* a, int32_t* nblk_out, void* stream) {
-  if (!a || !a->image || !a->gt || !a->partial || !a->grad_image || a->num_pixels < 1) return MGS_ERR_BAD_ARGUMENT;
-  if (a->apply_exposure && (!a->exposure_a || !a->exposure_b)) return MGS_ERR_BAD_ARGUMENT;
-  if (a->w_depth != 0.f && (!a->depth || !a->gt_depth || !a->grad_depth)) return MGS_ERR_BAD_ARGUMENT;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = a->num_pixels % 4 == 0 && al16(a->image) && al16(a->gt) && al16(a->mask) && al16(a->depth) &&
-                   al16(a->gt_depth) && al16(a->grad_image) && al16(a->grad_depth);
+  if (!map_args_ok(a) || !a->grad_image) return MGS_ERR_BAD_ARGUMENT;
+  if (a->w_depth != 0.f && !a->grad_depth) return MGS_ERR_BAD_ARGUMENT;
   int nb = loss_blocks(a->num_pixels);
-  if (vec) {
+  if (vec_ok(a->num_pixels, {a->image, a->gt, a->mask, a->depth, a->gt_depth, a->grad_image, a->grad_depth})) {
     nb = loss_blocks(a->num_pixels / 4);
-    launch("map_loss_fused", k_map_loss_fused<true>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+    launch("map_loss_fused", k_map_loss<true, true, true>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   } else {
-    launch("map_loss_fused", k_map_loss_fused<false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+    launch("map_loss_fused", k_map_loss<true, true, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   }
   if (nblk_out) *nblk_out = nb;
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
@@ -1034,70 +848,58 @@ int32_t mgs_sketch_assign(int64_t num_pixels, int32_t stack_dim, int32_t sketch_
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
-int32_t mgs_sketch_residual(const mgs_sketch_residual_args* a, void* stream) {
+static int32_t sketch_residual(const mgs_sketch_residual_args* a, const mgs_tracking_depth_args* d, bool rgbd, void* stream) {
   if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->bucket ||
       !a->weights || !a->grad_image || !a->Sf || !a->sj_exposure || !a->l1 || a->num_pixels < 1 ||
       a->stack_dim < 1 || a->sketch_dim < 1)
     return MGS_ERR_BAD_ARGUMENT;
+  if (rgbd && (!d || !d->depth || !d->gt_depth || !d->grad_depth)) return MGS_ERR_BAD_ARGUMENT;
   const size_t smem = sizeof(float) * 3 * (size_t)a->stack_dim * a->sketch_dim;
   if (smem > 48 * 1024) return MGS_ERR_UNSUPPORTED;
   const int64_t want = (a->num_pixels + kSketchThreads - 1) / kSketchThreads;
   const int nb = (int)(want < kSketchBlocks ? want : kSketchBlocks);
   SketchKeys K = {0, 0, 0, 0u, 0u, 0u};
   if (a->assign && !sketch_keys(a->num_pixels, a->stack_dim, a->sketch_dim, a->assign_key, K)) return MGS_ERR_BAD_ARGUMENT;
-  launch_smem("sketch_residual", k_sketch_residual, dim3(nb), dim3(kSketchThreads), smem, (hipStream_t)stream, *a, K);
+  if (rgbd)
+    launch_smem("sketch_residual_rgbd", k_sketch_residual_rgbd, dim3(nb), dim3(kSketchThreads), smem, (hipStream_t)stream,
+                *a, K, *d);
+  else
+    launch_smem("sketch_residual", k_sketch_residual, dim3(nb), dim3(kSketchThreads), smem, (hipStream_t)stream, *a, K);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
+int32_t mgs_sketch_residual(const mgs_sketch_residual_args* a, void* stream) {
+  return sketch_residual(a, nullptr, false, stream);
+}
+
 int32_t mgs_sketch_residual_rgbd(const mgs_sketch_residual_args* a, const mgs_tracking_depth_args* d, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->bucket ||
-      !a->weights || !a->grad_image || !a->Sf || !a->sj_exposure || !a->l1 || a->num_pixels < 1 ||
-      a->stack_dim < 1 || a->sketch_dim < 1 || !d || !d->depth || !d->gt_depth || !d->grad_depth)
-    return MGS_ERR_BAD_ARGUMENT;
-  const size_t smem = sizeof(float) * 3 * (size_t)a->stack_dim * a->sketch_dim;
-  if (smem > 48 * 1024) return MGS_ERR_UNSUPPORTED;
-  const int64_t want = (a->num_pixels + kSketchThreads - 1) / kSketchThreads;
-  const int nb = (int)(want < kSketchBlocks ? want : kSketchBlocks);
-  SketchKeys K = {0, 0, 0, 0u, 0u, 0u};
-  if (a->assign && !sketch_keys(a->num_pixels, a->stack_dim, a->sketch_dim, a->assign_key, K)) return MGS_ERR_BAD_ARGUMENT;
-  launch_smem("sketch_residual_rgbd", k_sketch_residual_rgbd, dim3(nb), dim3(kSketchThreads), smem, (hipStream_t)stream,
-              *a, K, *d);
-  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+  return sketch_residual(a, d, true, stream);
 }
 
 int32_t mgs_tracking_loss_partial_count(int64_t num_pixels) { return 4 * loss_blocks(num_pixels); }
 
-// p of the norm: <= 0 selects 2; 0 < p < 1 is not a norm (and its derivative is unbounded at 0)
-static bool pnorm_ok(float p) { return !(p > 0.f && p < 1.f) && p == p; }
+// What every tracking-loss entry needs (inputs, exposure, partial, a size, p of the norm: <= 0 selects 2, 0 < p < 1 is
+// not a norm and its derivative is unbounded at 0) and, in `need`, what this one needs beyond that.
+enum { kScalars = 1, kGradOut = 2, kGradImage = 4, kGradAB = 8 };
 
-// Fused form used by mgs_tracking_iteration: forward sums + backward in two launches; the
-// exposure partials ([2, nblk]) start at partial + nblk.
-int32_t mgs_tracking_loss_fused(const mgs_tracking_loss_args* a, int32_t* nblk_out, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
-      !a->scalars || !a->grad_out || !a->grad_image || a->num_pixels < 1)
-    return MGS_ERR_BAD_ARGUMENT;
-  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
-  const int nb = loss_blocks(a->num_pixels);
-  launch("track_loss_fwd", k_track_loss_fwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
-  launch("track_loss_bwd", k_track_loss_bwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
-  if (nblk_out) *nblk_out = nb;
-  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+static bool track_args_ok(const mgs_tracking_loss_args* a, int need) {
+  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial || a->num_pixels < 1)
+    return false;
+  if ((need & kScalars) && !a->scalars) return false;
+  if ((need & kGradOut) && !a->grad_out) return false;
+  if ((need & kGradImage) && !a->grad_image) return false;
+  if ((need & kGradAB) && (!a->grad_a || !a->grad_b)) return false;
+  return !(a->pnorm > 0.f && a->pnorm < 1.f) && a->pnorm == a->pnorm;
 }
 
 int32_t mgs_tracking_loss_onepass(const mgs_tracking_loss_args* a, int32_t* nblk_out, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
-      !a->grad_image || a->num_pixels < 1)
-    return MGS_ERR_BAD_ARGUMENT;
-  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
-  auto al16 = [](const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; };
-  const bool vec = a->num_pixels % 4 == 0 && al16(a->image) && al16(a->opacity) && al16(a->gt) && al16(a->mask) &&
-                   al16(a->grad_image);
+  if (!track_args_ok(a, kGradImage)) return MGS_ERR_BAD_ARGUMENT;
   int nb = loss_blocks(a->num_pixels);
-  if (vec) {
+  if (vec_ok(a->num_pixels, {a->image, a->opacity, a->gt, a->mask, a->grad_image})) {
     nb = loss_blocks(a->num_pixels / 4);
-    launch("track_loss", k_track_loss_onepass<true>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+    launch("track_loss", k_track_loss<true, true, true>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   } else {
-    launch("track_loss", k_track_loss_onepass<false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+    launch("track_loss", k_track_loss<true, true, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
   }
   if (nblk_out) *nblk_out = nb;
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
@@ -1105,37 +907,28 @@ int32_t mgs_tracking_loss_onepass(const mgs_tracking_loss_args* a, int32_t* nblk
 
 int32_t mgs_tracking_loss_rgbd_fused(const mgs_tracking_loss_args* a, const mgs_tracking_depth_args* d,
                                      int32_t* nblk_out, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
-      !a->grad_image || a->num_pixels < 1 || !d || !d->depth || !d->gt_depth || !d->grad_depth)
-    return MGS_ERR_BAD_ARGUMENT;
-  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
+  if (!track_args_ok(a, kGradImage) || !d || !d->depth || !d->gt_depth || !d->grad_depth) return MGS_ERR_BAD_ARGUMENT;
   const int nb = loss_blocks(a->num_pixels);
   launch("track_loss_rgbd", k_track_loss_rgbd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a, *d);
   if (a->scalars)
-    launch("track_loss_rgbd_fin", k_track_loss_rgbd_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
+    launch("track_loss_rgbd_fin", k_track_loss_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb, 1, 1);
   if (nblk_out) *nblk_out = nb;
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 int32_t mgs_tracking_loss_forward(const mgs_tracking_loss_args* a, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
-      !a->scalars || a->num_pixels < 1)
-    return MGS_ERR_BAD_ARGUMENT;
-  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
+  if (!track_args_ok(a, kScalars)) return MGS_ERR_BAD_ARGUMENT;
   const int nb = loss_blocks(a->num_pixels);
-  launch("track_loss_fwd", k_track_loss_fwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
-  launch("track_loss_finish", k_track_loss_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
+  launch("track_loss_fwd", k_track_loss<true, false, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+  launch("track_loss_finish", k_track_loss_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb, 1, 0);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 int32_t mgs_tracking_loss_backward(const mgs_tracking_loss_args* a, void* stream) {
-  if (!a || !a->image || !a->opacity || !a->gt || !a->exposure_a || !a->exposure_b || !a->partial ||
-      !a->scalars || !a->grad_out || !a->grad_image || !a->grad_a || !a->grad_b || a->num_pixels < 1)
-    return MGS_ERR_BAD_ARGUMENT;
-  if (!pnorm_ok(a->pnorm)) return MGS_ERR_BAD_ARGUMENT;
+  if (!track_args_ok(a, kScalars | kGradOut | kGradImage | kGradAB)) return MGS_ERR_BAD_ARGUMENT;
   const int nb = loss_blocks(a->num_pixels);
-  launch("track_loss_bwd", k_track_loss_bwd, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a, 0);
-  launch("track_loss_bwd_fin", k_track_loss_bwd_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb);
+  launch("track_loss_bwd", k_track_loss<false, true, false>, dim3(nb), dim3(kLossBlock), (hipStream_t)stream, *a);
+  launch("track_loss_bwd_fin", k_track_loss_finish, dim3(1), dim3(kLossBlock), (hipStream_t)stream, *a, nb, 0, 1);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 

@@ -19,6 +19,36 @@ def _stream(dev):
     return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
+def _ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def _tracking_args(image, opacity, gt, mask, exposure_a, exposure_b, eps, delta, HW, pnorm, partial, scalars, **grads):
+    """mgs_tracking_loss_args of contiguous fp32 tensors (mask may be None); `grads`: the backward's fields."""
+    a = _cabi.TrackingLossArgs()
+    a.image, a.opacity, a.gt, a.mask = _ptr(image), _ptr(opacity), _ptr(gt), _ptr(mask)
+    a.exposure_a, a.exposure_b = _ptr(exposure_a), _ptr(exposure_b)
+    a.exposure_eps, a.huber_delta, a.num_pixels, a.pnorm = float(eps), float(delta), HW, float(pnorm)
+    a.partial, a.scalars = _ptr(partial), _ptr(scalars)
+    for name, t in grads.items():
+        setattr(a, name, _ptr(t))
+    return a
+
+
+def _mapping_args(image, gt, mask, depth, gt_depth, exposure_a, exposure_b, eps, w_rgb, w_depth, thr, apply_exposure,
+                  HW, partial, loss, **grads):
+    """mgs_mapping_loss_args of contiguous fp32 tensors (None: absent); `grads`: grad_out and the outputs."""
+    a = _cabi.MappingLossArgs()
+    a.image, a.gt, a.mask, a.depth, a.gt_depth = _ptr(image), _ptr(gt), _ptr(mask), _ptr(depth), _ptr(gt_depth)
+    a.exposure_a, a.exposure_b = _ptr(exposure_a), _ptr(exposure_b)
+    a.exposure_eps, a.w_rgb, a.w_depth = float(eps), float(w_rgb), float(w_depth)
+    a.depth_mask_threshold, a.apply_exposure, a.num_pixels = float(thr), int(apply_exposure), HW
+    a.partial, a.loss = _ptr(partial), _ptr(loss)
+    for name, t in grads.items():
+        setattr(a, name, _ptr(t))
+    return a
+
+
 class _TrackingLoss(torch.autograd.Function):
     @staticmethod
     def forward(ctx, image, opacity, gt, mask, exposure_a, exposure_b, exposure_eps, huber_delta, pnorm=2.0):
@@ -33,13 +63,8 @@ class _TrackingLoss(torch.autograd.Function):
         HW = int(image_c.shape[-1] * image_c.shape[-2])
         partial = torch.empty(int(lib.mgs_tracking_loss_partial_count(HW)), dtype=torch.float32, device=dev)
         scalars = torch.empty(2, dtype=torch.float32, device=dev)
-        a = _cabi.TrackingLossArgs()
-        a.image, a.opacity, a.gt = image_c.data_ptr(), opa_c.data_ptr(), gt_c.data_ptr()
-        a.mask = None if mask_c is None else mask_c.data_ptr()
-        a.exposure_a, a.exposure_b = exposure_a.data_ptr(), exposure_b.data_ptr()
-        a.exposure_eps, a.huber_delta, a.num_pixels = float(exposure_eps), float(huber_delta), HW
-        a.pnorm = float(pnorm)
-        a.partial, a.scalars = partial.data_ptr(), scalars.data_ptr()
+        a = _tracking_args(image_c, opa_c, gt_c, mask_c, exposure_a, exposure_b, exposure_eps, huber_delta, HW, pnorm,
+                           partial, scalars)
         _cabi.check(lib.mgs_tracking_loss_forward(C.byref(a), _stream(dev)), "mgs_tracking_loss_forward")
         ctx.save_for_backward(image_c, opa_c, gt_c, mask_c, exposure_a, exposure_b, partial, scalars)
         ctx.consts = (float(exposure_eps), float(huber_delta), HW, float(pnorm))
@@ -57,15 +82,8 @@ class _TrackingLoss(torch.autograd.Function):
         g_img = torch.empty_like(image_c)
         g_a = torch.empty(1, dtype=torch.float32, device=dev)
         g_b = torch.empty(1, dtype=torch.float32, device=dev)
-        a = _cabi.TrackingLossArgs()
-        a.image, a.opacity, a.gt = image_c.data_ptr(), opa_c.data_ptr(), gt_c.data_ptr()
-        a.mask = None if mask_c is None else mask_c.data_ptr()
-        a.exposure_a, a.exposure_b = exposure_a.data_ptr(), exposure_b.data_ptr()
-        a.exposure_eps, a.huber_delta, a.num_pixels = eps, delta, HW
-        a.pnorm = pnorm
-        a.partial, a.scalars = partial.data_ptr(), scalars.data_ptr()
-        a.grad_out, a.grad_image = go.data_ptr(), g_img.data_ptr()
-        a.grad_a, a.grad_b = g_a.data_ptr(), g_b.data_ptr()
+        a = _tracking_args(image_c, opa_c, gt_c, mask_c, exposure_a, exposure_b, eps, delta, HW, pnorm, partial, scalars,
+                           grad_out=go, grad_image=g_img, grad_a=g_a, grad_b=g_b)
         _cabi.check(lib.mgs_tracking_loss_backward(C.byref(a), _stream(dev)), "mgs_tracking_loss_backward")
         return (g_img, None, None, None, g_a.reshape(exposure_a.shape), g_b.reshape(exposure_b.shape),
                 None, None, None)
@@ -100,14 +118,8 @@ class _TrackingLossRGBD(torch.autograd.Function):
         out = torch.empty(4, dtype=torch.float32, device=dev)         # loss, loss^(1-p), d/da, d/db
         g_img = torch.empty_like(image_c)
         g_dep = torch.empty_like(depth_c)
-        a = _cabi.TrackingLossArgs()
-        a.image, a.opacity, a.gt = image_c.data_ptr(), opa_c.data_ptr(), gt_c.data_ptr()
-        a.mask = None if mask_c is None else mask_c.data_ptr()
-        a.exposure_a, a.exposure_b = exposure_a.data_ptr(), exposure_b.data_ptr()
-        a.exposure_eps, a.huber_delta, a.num_pixels = float(exposure_eps), float(huber_delta), HW
-        a.pnorm = float(pnorm)
-        a.partial, a.scalars = partial.data_ptr(), out.data_ptr()
-        a.grad_image, a.grad_a, a.grad_b = g_img.data_ptr(), out[2:].data_ptr(), out[3:].data_ptr()
+        a = _tracking_args(image_c, opa_c, gt_c, mask_c, exposure_a, exposure_b, exposure_eps, huber_delta, HW, pnorm,
+                           partial, out, grad_image=g_img, grad_a=out[2:], grad_b=out[3:])
         d = _cabi.TrackingDepthArgs()
         d.depth, d.gt_depth, d.grad_depth = depth_c.data_ptr(), gtd_c.data_ptr(), g_dep.data_ptr()
         d.w_rgb, d.w_depth = float(alpha), 1.0 - float(alpha)
@@ -226,15 +238,11 @@ class _MappingLoss(torch.autograd.Function):
         f = lambda t: None if t is None else t.detach().float().contiguous()
         image_c, depth_c, gt_c, gtd_c, mask_c = f(image), f(depth), f(gt), f(gt_depth), f(mask)
         HW = int(image_c.shape[-1] * image_c.shape[-2])
-        partial = _zeroed_partials(dev, int(lib.mgs_tracking_loss_partial_count(HW)))
+        # (a scratch of its own: the one-pass kernel may run fewer workgroups, its ticket then sits among these sums)
+        partial = _zeroed_partials(dev, int(lib.mgs_mapping_loss_partial_count(HW)), kind="mapping_fwd_bwd")
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        a = _cabi.MappingLossArgs()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        a.image, a.gt, a.mask, a.depth, a.gt_depth = ptr(image_c), ptr(gt_c), ptr(mask_c), ptr(depth_c), ptr(gtd_c)
-        a.exposure_a, a.exposure_b = ptr(exposure_a), ptr(exposure_b)
-        a.exposure_eps, a.w_rgb, a.w_depth = float(exposure_eps), float(w_rgb), float(w_depth)
-        a.depth_mask_threshold, a.apply_exposure, a.num_pixels = float(depth_mask_threshold), int(apply_exposure), HW
-        a.partial, a.loss = partial.data_ptr(), loss.data_ptr()
+        a = _mapping_args(image_c, gt_c, mask_c, depth_c, gtd_c, exposure_a, exposure_b, exposure_eps, w_rgb, w_depth,
+                          depth_mask_threshold, apply_exposure, HW, partial, loss)
         a.partial_ticket_ready = 1          # one launch: the last workgroup finishes the sum
         _cabi.check(lib.mgs_mapping_loss_forward(C.byref(a), _stream(dev)), "mgs_mapping_loss_forward")
         ctx.save_for_backward(image_c, depth_c, gt_c, gtd_c, mask_c, exposure_a, exposure_b, partial)
@@ -256,14 +264,9 @@ class _MappingLoss(torch.autograd.Function):
         g_a = torch.empty(1, dtype=torch.float32, device=dev) if apply_exposure else None
         g_b = torch.empty(1, dtype=torch.float32, device=dev) if apply_exposure else None
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        a = _cabi.MappingLossArgs()
-        ptr = lambda t: None if t is None else t.data_ptr()
-        a.image, a.gt, a.mask, a.depth, a.gt_depth = ptr(image_c), ptr(gt_c), ptr(mask_c), ptr(depth_c), ptr(gtd_c)
-        a.exposure_a, a.exposure_b = ptr(exposure_a), ptr(exposure_b)
-        a.exposure_eps, a.w_rgb, a.w_depth = eps, w_rgb, w_depth
-        a.depth_mask_threshold, a.apply_exposure, a.num_pixels = thr, apply_exposure, HW
-        a.partial, a.loss, a.grad_out = partial.data_ptr(), loss.data_ptr(), go.data_ptr()
-        a.grad_image, a.grad_depth, a.grad_a, a.grad_b = ptr(g_img), ptr(g_dep), ptr(g_a), ptr(g_b)
+        a = _mapping_args(image_c, gt_c, mask_c, depth_c, gtd_c, exposure_a, exposure_b, eps, w_rgb, w_depth, thr,
+                          apply_exposure, HW, partial, loss, grad_out=go, grad_image=g_img, grad_depth=g_dep,
+                          grad_a=g_a, grad_b=g_b)
         _cabi.check(lib.mgs_mapping_loss_backward(C.byref(a), _stream(dev)), "mgs_mapping_loss_backward")
         ga = None if g_a is None else g_a.reshape(exposure_a.shape)
         gb = None if g_b is None else g_b.reshape(exposure_b.shape)
@@ -308,18 +311,13 @@ def l1_image_depth_loss_backward(image, depth, gt_image, gt_depth, w_depth=0.05,
     g_img = torch.empty_like(image_c)
     g_dep = torch.empty_like(depth_c) if use_depth else None
     out = torch.empty(3, dtype=torch.float32, device=dev)        # loss, d/da, d/db
-    a = _cabi.MappingLossArgs()
-    ptr = lambda t: None if t is None else t.data_ptr()
-    a.image, a.gt, a.mask = ptr(image_c), ptr(gt_c), ptr(mask_c)
-    a.depth, a.gt_depth = (ptr(depth_c), ptr(gtd_c)) if use_depth else (None, None)
-    if viewpoint is not None:
-        a.exposure_a, a.exposure_b = viewpoint.exposure_a.data_ptr(), viewpoint.exposure_b.data_ptr()
-        a.exposure_eps, a.apply_exposure = float(viewpoint.exposure_eps), 1
-        a.grad_a, a.grad_b = out[1:].data_ptr(), out[2:].data_ptr()
-    a.w_rgb, a.w_depth = float(w_rgb), float(w_depth) if use_depth else 0.0
-    a.depth_mask_threshold, a.num_pixels = float(depth_mask_threshold), HW
-    a.partial, a.grad_image, a.grad_depth = partial.data_ptr(), g_img.data_ptr(), ptr(g_dep)
-    a.loss, a.partial_ticket_ready = out.data_ptr(), 1            # the last workgroup finishes the sums
+    vp = viewpoint
+    a = _mapping_args(image_c, gt_c, mask_c, depth_c if use_depth else None, gtd_c if use_depth else None,
+                      None if vp is None else vp.exposure_a, None if vp is None else vp.exposure_b,
+                      0.0 if vp is None else vp.exposure_eps, w_rgb, w_depth if use_depth else 0.0, depth_mask_threshold,
+                      0 if vp is None else 1, HW, partial, out, grad_image=g_img, grad_depth=g_dep,
+                      grad_a=None if vp is None else out[1:], grad_b=None if vp is None else out[2:])
+    a.partial_ticket_ready = 1            # the last workgroup finishes the sums
     _cabi.check(lib.mgs_mapping_loss_fused(C.byref(a), None, _stream(dev)), "mgs_mapping_loss_fused")
     tensors, grads = [image], [g_img.view_as(image)]
     if use_depth and depth.requires_grad:

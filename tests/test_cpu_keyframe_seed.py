@@ -190,7 +190,7 @@ def test_struct_mirror_and_exports(built):
     assert _cabi.struct_mirrors()[25] is _cabi.KeyframeSeedArgs
     assert C.sizeof(_cabi.KeyframeSeedResult) == 32
     assert {"mgs_keyframe_seed_scratch_bytes", "mgs_keyframe_seed"} <= set(_cabi.EXPORTS)
-    assert L.mgs_abi_version() == 9
+    assert L.mgs_abi_version() == 10
     assert L.mgs_keyframe_seed_scratch_bytes(0, 10) == 0 and L.mgs_keyframe_seed_scratch_bytes(10, 0) == 0
     assert L.mgs_keyframe_seed_scratch_bytes(640 * 480, 9600) >= L.mgs_knn_scratch_bytes(9600) + 2 * 4 * 640 * 480
 

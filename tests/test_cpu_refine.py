@@ -55,8 +55,8 @@ def test_refinement_entry_points_are_exported(built):
     for name in ("mgs_ssim_loss", "mgs_ssim_loss_partial_count", "mgs_refine_view_iteration"):
         assert hasattr(lib, name)
         assert name in _cabi.EXPORTS
-    assert _cabi.ABI_VERSION == 9
-    assert _cabi.lib().mgs_abi_version() == 9
+    assert _cabi.ABI_VERSION == 10
+    assert _cabi.lib().mgs_abi_version() == 10
 
 
 def test_refinement_struct_mirrors(built):

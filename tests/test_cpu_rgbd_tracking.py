@@ -88,6 +88,6 @@ def test_rgbd_entry_points_are_exported_and_mirrored(built):
         assert hasattr(lib, name)
         assert name in _cabi.EXPORTS
     L = _cabi.lib()
-    assert L.mgs_abi_version() == 9
+    assert L.mgs_abi_version() == 10
     assert L.mgs_struct_size(22) == C.sizeof(_cabi.TrackingDepthArgs) == 40
     assert _cabi.struct_mirrors()[22] is _cabi.TrackingDepthArgs

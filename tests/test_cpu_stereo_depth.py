@@ -216,4 +216,4 @@ def test_entry_points_and_argument_checks_without_a_gpu(built):
     a = _cabi.StereoDepthArgs()
     a.width, a.height, a.num_disparities, a.block_size, a.uniqueness_ratio = 100, 10, 64, 20, 40
     assert L.mgs_stereo_depth(C.byref(a), None) == -1               # null pointers: refused before anything is launched
-    assert _cabi.ABI_VERSION == 9
+    assert _cabi.ABI_VERSION == 10

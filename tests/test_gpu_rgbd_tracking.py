@@ -43,13 +43,15 @@ def test_hip_rgbd_loss_matches_torch_autograd(built):
     from monogs_amd.tracking_fused import tracking_loss_rgbd
     dev = torch.device("cuda:0")
     g = torch.Generator().manual_seed(0)
-    H, W = 120, 160
 
     class VP:
         pass
 
-    for delta, a0, pn, alpha in ((0.01, 0.9, 2.0, 0.95), (0.0, -1.1, 2.0, 0.9), (0.0, 0.9, 1.0, 0.95),
-                                 (0.01, -1.1, 1.0, 0.9), (0.0, 1.05, 1.5, 0.95), (0.01, 0.9, 1.5, 0.9)):
+    # 120x160, then 363x365: an odd count past one trip of the kernel's grid
+    cases = [(H, W, *c) for H, W in ((120, 160), (363, 365))
+             for c in ((0.01, 0.9, 2.0, 0.95), (0.0, -1.1, 2.0, 0.9), (0.0, 0.9, 1.0, 0.95),
+                       (0.01, -1.1, 1.0, 0.9), (0.0, 1.05, 1.5, 0.95), (0.01, 0.9, 1.5, 0.9))]
+    for H, W, delta, a0, pn, alpha in cases:
         vp = VP()
         vp.original_image = torch.rand(3, H, W, generator=g).to(dev)
         vp.rgb_pixel_mask_mapping = (torch.rand(1, H, W, generator=g) > 0.2).to(dev)
@@ -74,8 +76,8 @@ def test_hip_rgbd_loss_matches_torch_autograd(built):
         got = tracking_loss_rgbd(img, dep, opa, vp, alpha, delta, pn)
         (2.5 * got).backward()
         tol = 1e-5 if pn != 1.5 else 1e-4
-        assert abs(got.item() - want[0]) <= 1e-5 * want[0], (delta, pn)
-        assert rel_err(img.grad, want[1]) < tol and rel_err(dep.grad, want[2]) < tol, (delta, pn)
+        assert abs(got.item() - want[0]) <= 1e-5 * want[0], (H, W, delta, pn)
+        assert rel_err(img.grad, want[1]) < tol and rel_err(dep.grad, want[2]) < tol, (H, W, delta, pn)
         assert rel_err(vp.exposure_a.grad, want[3]) < 1e-4 and rel_err(vp.exposure_b.grad, want[4]) < 1e-4
 
 

@@ -713,13 +713,15 @@ def test_fused_tracking_loss_matches_torch_reference(built):
     from monogs_amd.tracking_fused import tracking_loss
     dev = _dev()
     g = torch.Generator().manual_seed(0)
-    H, W = 120, 160
 
     class VP:
         pass
 
-    for delta, a0, pn in ((0.01, 0.9, 2.0), (0.0, -1.1, 2.0), (0.0, 0.9, 1.0), (0.0, -1.1, 1.0), (0.0, 1.05, 1.5),
-                          (0.01, 0.9, 1.0)):
+    # 120x160; 363x365 (odd, past one trip of the scalar kernels' grid) and 76x132 (whole float4s) after it
+    cases = [(H, W, *c) for H, W in ((120, 160), (363, 365), (76, 132))
+             for c in ((0.01, 0.9, 2.0), (0.0, -1.1, 2.0), (0.0, 0.9, 1.0), (0.0, -1.1, 1.0), (0.0, 1.05, 1.5),
+                       (0.01, 0.9, 1.0))]
+    for H, W, delta, a0, pn in cases:
         vp = VP()
         vp.original_image = torch.rand(3, H, W, generator=g).to(dev)
         vp.rgb_pixel_mask_mapping = (torch.rand(1, H, W, generator=g) > 0.2).to(dev)
@@ -740,8 +742,8 @@ def test_fused_tracking_loss_matches_torch_reference(built):
         vp.exposure_b.grad = None
         got = tracking_loss(img, opa, vp, delta, pn)
         (2.5 * got).backward()
-        assert abs(got.item() - want[0]) <= 1e-5 * want[0], (delta, pn)
-        assert rel_err(img.grad, want[1]) < (1e-5 if pn != 1.5 else 1e-4), (delta, pn)
+        assert abs(got.item() - want[0]) <= 1e-5 * want[0], (H, W, delta, pn)
+        assert rel_err(img.grad, want[1]) < (1e-5 if pn != 1.5 else 1e-4), (H, W, delta, pn)
         assert rel_err(vp.exposure_a.grad, want[2]) < 1e-4 and rel_err(vp.exposure_b.grad, want[3]) < 1e-4
 
 
@@ -1579,11 +1581,12 @@ def test_tile_scan_handoff_never_reads_stale_counts(built):
     assert abs(int(toff[T]) - em.pairs) <= max(2, em.pairs // 1000)
 
 
-@pytest.mark.parametrize("H,W", [(75, 133), (76, 132)])
+@pytest.mark.parametrize("H,W", [(75, 133), (76, 132), (1024, 516)])
 def test_fused_loss_backward_helper_matches_autograd(built, H, W):
     """l1_image_depth_loss_backward: value + gradients in one launch, handed to autograd - equal to
     loss.backward() of the torch formulation incl. the exposure path and the masks.  75x133 pixels are
-    not a multiple of 4 (scalar form of k_map_loss_fused), 76x132 are (four pixels per thread)."""
+    not a multiple of 4 (scalar form of k_map_loss), 76x132 are (four pixels per thread), 1024x516 need a second
+    trip of the four-pixel form."""
     from monogs_amd.tracking_fused import l1_image_depth_loss_backward
     dev = _dev()
     g = torch.Generator().manual_seed(5)
