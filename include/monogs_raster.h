@@ -1223,6 +1223,77 @@ typedef struct mgs_refine_view_args {
 
 int32_t mgs_refine_view_iteration(const mgs_refine_view_args* args, void* stream);
 
+/* ---- evaluation (utils/eval_utils.py:114-178; DESIGN.md: "Evaluation on the device") -------------------- */
+
+/* One launch scores a rendered view against its ground truth and writes ONE record of a caller-owned device table;
+ * nothing is read on the host.  With x = clamp(image, 0, 1), or x = clamp((|a| + eps) image + b, 0, 1) when
+ * apply_exposure != 0 (a = *exposure_a, b = *exposure_b), and y the ground truth (a uint8 [H,W,3] image is converted as
+ * the dataset does, / 255, while it is loaded), the record is MGS_EVAL_RECORD_DOUBLES doubles:
+ *   [MGS_EVAL_SSE]        sum (x - y)^2 over the ELEMENTS (channel by channel) with y > 0     (eval_utils.py:150-152)
+ *   [MGS_EVAL_SSE_ALL]    sum (x - y)^2 over all 3 H W elements                               (image_utils.py:19-21 as is)
+ *   [MGS_EVAL_ABS]        sum |x - y| over all 3 H W elements
+ *   [MGS_EVAL_SSIM]       sum S(x, y) over all 3 H W elements, S the SSIM map of mgs_ssim_loss (loss_utils.py:61-101)
+ *   [MGS_EVAL_DEPTH_ABS]  sum |depth - gt_depth| over the pixels with gt_depth > 0 (0 without depth)
+ *   [MGS_EVAL_N_MASK]     number of elements with y > 0
+ *   [MGS_EVAL_N_DEPTH]    number of pixels with gt_depth > 0
+ *   [MGS_EVAL_PAIRS]      *pair_count (the forward's pair count D of this view), 0 when pair_count is NULL
+ * Every workgroup writes its seven fp32 partial sums in a fixed order and the workgroup that takes the last ticket adds
+ * them in index order in double: no float atomics, two calls give the same bits.  `partial` holds
+ * mgs_eval_score_partial_count(H, W) floats; its last slot is an int ticket that must be zero when the FIRST call on
+ * the buffer is enqueued (every call restores it), so calls in stream order may share the buffer. */
+#define MGS_EVAL_RECORD_DOUBLES 8
+#define MGS_EVAL_SSE 0
+#define MGS_EVAL_SSE_ALL 1
+#define MGS_EVAL_ABS 2
+#define MGS_EVAL_SSIM 3
+#define MGS_EVAL_DEPTH_ABS 4
+#define MGS_EVAL_N_MASK 5
+#define MGS_EVAL_N_DEPTH 6
+#define MGS_EVAL_PAIRS 7
+#define MGS_EVAL_GT_F32_CHW 0
+#define MGS_EVAL_GT_U8_HWC 1
+
+typedef struct mgs_eval_score_args {
+  int32_t height, width;
+  int32_t gt_format;             /* MGS_EVAL_GT_F32_CHW: float [3,H,W]; MGS_EVAL_GT_U8_HWC: uint8 [H,W,3] */
+  int32_t row, num_rows;         /* the record written, rows of `table`: 0 <= row < num_rows */
+  int32_t apply_exposure;        /* != 0: exposure_a / exposure_b are read */
+  float exposure_eps;
+  int32_t reserved0;
+  const float* image;            /* [3,H,W] the raw render */
+  const void* gt;                /* see gt_format */
+  const float* depth;            /* [H,W] rendered depth, or NULL */
+  const float* gt_depth;         /* [H,W], or NULL (both or neither) */
+  const float* exposure_a;       /* [1] */
+  const float* exposure_b;       /* [1] */
+  const int32_t* pair_count;     /* [1] or NULL */
+  float* partial;                /* scratch, see above */
+  double* table;                 /* [num_rows, MGS_EVAL_RECORD_DOUBLES] */
+} mgs_eval_score_args;
+
+/* Floats of mgs_eval_score_args.partial for an [3,H,W] image; -1 for a size the kernel is not built for. */
+int32_t mgs_eval_score_partial_count(int32_t height, int32_t width);
+int32_t mgs_eval_score(const mgs_eval_score_args* args, void* stream);
+
+/* One scored view as a fixed launch sequence with no host round trip:
+ *   camera matrices from T (skipped when camera_matrices_valid) -> rasteriser forward at the caller's fixed pair
+ *   capacity -> mgs_eval_score(out_color, and out_depth when score.gt_depth is given) into record score.row.
+ * score.image / depth / pair_count are filled in by the call (pair_count: the forward's counter in `geom`, so a record
+ * whose MGS_EVAL_PAIRS exceeds fwd.shape.pair_capacity was rendered incompletely and has to be scored again);
+ * score.height / width must equal fwd.shape's. */
+typedef struct mgs_eval_view_args {
+  mgs_forward_args fwd;
+  const float* T;                /* [4,4] world -> camera */
+  mgs_eval_score_args score;
+  int32_t camera_matrices_valid;
+  int32_t reserved0;
+} mgs_eval_view_args;
+
+int32_t mgs_eval_view(const mgs_eval_view_args* args, void* stream);
+/* sizeof() of the two structs above, for a binding to verify its mirrors (as mgs_frame_prepare_args_size). */
+int32_t mgs_eval_score_args_size(void);
+int32_t mgs_eval_view_args_size(void);
+
 /* ---- dense Gauss-Newton tracking iteration ("Dense Gauss-Newton tracking") -----------------
  * The second-order iteration WITHOUT the sketch: every pixel p is a row of its own,
  *   f_p = s * sum_c Huber(r_pc),  s = stack_dim * sketch_dim / (H*W),  J_p = d f_p / d [rho; theta; a; b]

@@ -35,6 +35,8 @@ EXPORTS = (
     "mgs_stereo_depth_args_size", "mgs_stereo_scratch_bytes", "mgs_stereo_depth",
     "mgs_tracking_gn_args_size", "mgs_gauss_newton_scratch_bytes", "mgs_tracking_iteration_gauss_newton",
     "mgs_tracking_iteration_gauss_newton_rgbd", "mgs_normal_equations",
+    "mgs_eval_score", "mgs_eval_score_partial_count", "mgs_eval_score_args_size", "mgs_eval_view_args_size",
+    "mgs_eval_view",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -304,6 +306,23 @@ class StereoDepthArgs(C.Structure):
                                       "scratch")])
 
 
+EVAL_RECORD_DOUBLES = 8    # MGS_EVAL_RECORD_DOUBLES; the indices below are MGS_EVAL_*
+(EVAL_SSE, EVAL_SSE_ALL, EVAL_ABS, EVAL_SSIM, EVAL_DEPTH_ABS, EVAL_N_MASK, EVAL_N_DEPTH, EVAL_PAIRS) = range(8)
+EVAL_GT_F32_CHW, EVAL_GT_U8_HWC = 0, 1
+
+
+class EvalScoreArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("height", "width", "gt_format", "row", "num_rows", "apply_exposure")]
+                + [("exposure_eps", C.c_float), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("image", "gt", "depth", "gt_depth", "exposure_a", "exposure_b", "pair_count",
+                                      "partial", "table")])
+
+
+class EvalViewArgs(C.Structure):
+    _fields_ = [("fwd", ForwardArgs), ("T", _fp), ("score", EvalScoreArgs), ("camera_matrices_valid", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
 _lib = None
 
 
@@ -463,6 +482,16 @@ def lib():
     L.mgs_tracking_iteration_gauss_newton_rgbd.argtypes = [C.POINTER(TrackingGNArgs), _dp, C.c_void_p]
     L.mgs_normal_equations.restype = C.c_int32
     L.mgs_normal_equations.argtypes = [C.POINTER(TrackingGNArgs), _dp, C.c_void_p]
+    for fn, cls in ((L.mgs_eval_score_args_size, EvalScoreArgs), (L.mgs_eval_view_args_size, EvalViewArgs)):
+        fn.restype, fn.argtypes = C.c_int32, []
+        if fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    L.mgs_eval_score_partial_count.restype = C.c_int32
+    L.mgs_eval_score_partial_count.argtypes = [C.c_int32, C.c_int32]
+    L.mgs_eval_score.restype = C.c_int32
+    L.mgs_eval_score.argtypes = [C.POINTER(EvalScoreArgs), C.c_void_p]
+    L.mgs_eval_view.restype = C.c_int32
+    L.mgs_eval_view.argtypes = [C.POINTER(EvalViewArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -11,7 +11,8 @@ map_update.py work on either):
   reset_opacity[_nonvisible]       :364-377   -> mgs_map_finish_iteration (reset_mode)
   prune / densify                  :485-691   -> map_update.py (plan + gather kernels)
   add_densification_stats          :693-697
-PLY I/O is not part of the path.  Differences by design: `unique_kfIDs` / `n_obs` are device
+  save_ply / load_ply              :314-362, :379-470 -> ply_io.py (one device concatenation, one copy)
+Differences by design: `unique_kfIDs` / `n_obs` are device
 int32 tensors (the reference keeps them on the CPU, forcing a sync per prune), and the
 optimiser is FusedGaussianAdam (one launch per step).
 """
@@ -132,6 +133,38 @@ class GaussianModel:
                 g["lr"] = expon_lr(iteration, self.lr_init, self.lr_final, lr_delay_mult=self.lr_delay_mult,
                                    max_steps=self.max_steps)
                 return g["lr"]
+
+    # ---- map export / import (:314-362, :379-470) -----------------------------------------------
+    def save_ply(self, path):
+        """The raw parameters as a binary little-endian PLY in the reference's layout (ply_io.py)."""
+        from .ply_io import write_gaussian_ply
+        write_gaussian_ply(path, self._xyz, self._features_dc, self._features_rest, self._opacity, self._scaling,
+                           self._rotation)
+
+    def load_ply(self, path):
+        """Replace the map by the one stored at `path` (:379-470): parameters on self.device, the active SH degree at
+        its maximum, statistics and per-Gaussian bookkeeping zeroed, no optimiser - call training_setup() next."""
+        from .ply_io import read_gaussian_ply
+        t = read_gaussian_ply(path)
+        K = (self.max_sh_degree + 1) ** 2
+        if t["features_rest"].shape[1] != K - 1:
+            raise ValueError(f"{path}: {3 * t['features_rest'].shape[1]} f_rest properties, max_sh_degree "
+                             f"{self.max_sh_degree} needs {3 * K - 3}")
+        if t["scaling"].shape[1] not in (1, 3) or t["rotation"].shape[1] != 4:
+            raise ValueError(f"{path}: {t['scaling'].shape[1]} scale and {t['rotation'].shape[1]} rot properties")
+        dev = self.device
+        par = lambda a: nn.Parameter(a.to(dev).contiguous().requires_grad_(True))
+        self._xyz, self._features_dc, self._features_rest = par(t["xyz"]), par(t["features_dc"]), par(t["features_rest"])
+        self._opacity, self._scaling, self._rotation = par(t["opacity"]), par(t["scaling"]), par(t["rotation"])
+        self.isotropic = t["scaling"].shape[1] == 1
+        self.active_sh_degree = self.max_sh_degree
+        n = len(self)
+        self.max_radii2D = torch.zeros(n, device=dev)
+        self.xyz_gradient_accum = torch.zeros(n, 1, device=dev)
+        self.denom = torch.zeros(n, 1, device=dev)
+        self.unique_kfIDs = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.n_obs = torch.zeros(n, dtype=torch.int32, device=dev)
+        self.optimizer = None
 
     # ---- keyframe insertion (:108-245) ------------------------------------------------------
     def create_pcd_from_image(self, cam, init=False, scale=2.0, depthmap=None, generator=None):

@@ -1,0 +1,114 @@
+"""The Gaussian map as a PLY file, in the layout of GaussianModel.save_ply / load_ply of the reference
+(gaussian_splatting/scene/gaussian_model.py:314-362, 379-470), which is what 3DGS viewers read:
+
+    ply / format binary_little_endian 1.0 / element vertex N / property float <name> ... / end_header
+    N rows of little-endian fp32 in the order of construct_list_of_attributes:
+    x y z  nx ny nz (zero)  f_dc_*  f_rest_*  opacity  scale_*  rot_*
+
+f_dc and f_rest are stored channel-major: the [N,K,3] parameter is written as transpose(1, 2).flatten(1), so f_rest_j
+is coefficient j % (K - 1) of channel j // (K - 1).  Every value is the RAW parameter (log scale, opacity logit,
+un-normalised quaternion).  An isotropic model has the single column scale_0.
+
+Free functions on plain tensors, no GPU needed.  `plyfile` is not used: the writer emits the bytes above itself, so the
+agreement with a file plyfile would write is by the PLY specification, not by comparison."""
+from __future__ import annotations
+
+import os
+from typing import Dict, List
+
+import numpy as np
+import torch
+
+
+def ply_attribute_names(n_dc: int, n_rest: int, n_scale: int, n_rot: int = 4) -> List[str]:
+    """construct_list_of_attributes (:314-326)."""
+    names = ["x", "y", "z", "nx", "ny", "nz"]
+    names += [f"f_dc_{i}" for i in range(n_dc)]
+    names += [f"f_rest_{i}" for i in range(n_rest)]
+    names.append("opacity")
+    names += [f"scale_{i}" for i in range(n_scale)]
+    names += [f"rot_{i}" for i in range(n_rot)]
+    return names
+
+
+def write_gaussian_ply(path: str, xyz, features_dc, features_rest, opacity, scaling, rotation) -> None:
+    """xyz [N,3], features_dc [N,1,3], features_rest [N,K-1,3], opacity [N,1], scaling [N,3] or [N,1], rotation [N,4].
+    The rows are concatenated on the tensors' device and copied to the host once."""
+    t = lambda a: a.detach().to(torch.float32)
+    xyz = t(xyz)
+    n = int(xyz.shape[0])
+    f_dc = t(features_dc).transpose(1, 2).flatten(1)
+    f_rest = t(features_rest).transpose(1, 2).flatten(1)
+    cols = (xyz, torch.zeros_like(xyz), f_dc, f_rest, t(opacity).reshape(n, 1), t(scaling).flatten(1),
+            t(rotation).flatten(1))
+    rows = torch.cat(cols, dim=1).contiguous().cpu().numpy().astype("<f4", copy=False)
+    names = ply_attribute_names(f_dc.shape[1], f_rest.shape[1], cols[5].shape[1], cols[6].shape[1])
+    assert rows.shape == (n, len(names))
+    header = ["ply", "format binary_little_endian 1.0", f"element vertex {n}"]
+    header += [f"property float {name}" for name in names]
+    header.append("end_header")
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(("\n".join(header) + "\n").encode("ascii"))
+        fh.write(rows.tobytes())
+
+
+def read_gaussian_ply(path: str) -> Dict[str, torch.Tensor]:
+    """The inverse of write_gaussian_ply: CPU float tensors xyz, features_dc [N,1,3], features_rest [N,K-1,3],
+    opacity [N,1], scaling, rotation.  Properties are found by name (f_rest_*, scale_*, rot_* in index order), as
+    load_ply (:379-470) finds them."""
+    with open(path, "rb") as fh:
+        blob = fh.read()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = blob[:end].decode("ascii").split("\n")
+    body = end + len(b"end_header\n")
+    if "format binary_little_endian 1.0" not in lines:
+        raise ValueError(f"{path}: only binary_little_endian 1.0 is read")
+    n, names, in_vertex, seen_vertex = 0, [], False, False
+    for ln in lines:
+        tok = ln.split()
+        if not tok:
+            continue
+        if tok[0] == "element":
+            if tok[1] != "vertex" and not seen_vertex:
+                raise ValueError(f"{path}: element {tok[1]} before the vertex element")
+            in_vertex = tok[1] == "vertex"
+            if in_vertex:
+                n, seen_vertex = int(tok[2]), True
+        elif tok[0] == "property" and in_vertex:
+            if tok[1] not in ("float", "float32"):
+                raise ValueError(f"{path}: property {tok[-1]} is {tok[1]}, not float")
+            names.append(tok[-1])
+    if not seen_vertex:
+        raise ValueError(f"{path}: no vertex element")
+    width = len(names)
+    if len(blob) - body < 4 * n * width:
+        raise ValueError(f"{path}: {n} x {width} floats expected, file too short")
+    rows = np.frombuffer(blob, dtype="<f4", count=n * width, offset=body).reshape(n, width).astype(np.float32)
+    col = {name: i for i, name in enumerate(names)}
+
+    def numbered(prefix):
+        found = [nm for nm in names if nm.startswith(prefix)]
+        return [col[nm] for nm in sorted(found, key=lambda s: int(s.split("_")[-1]))]
+
+    def take(idx):
+        return torch.from_numpy(np.ascontiguousarray(rows[:, idx]))
+
+    for need in ("x", "y", "z", "opacity", "f_dc_0", "f_dc_1", "f_dc_2"):
+        if need not in col:
+            raise ValueError(f"{path}: property {need} is missing")
+    rest = numbered("f_rest_")
+    if len(rest) % 3:
+        raise ValueError(f"{path}: {len(rest)} f_rest properties are no multiple of 3")
+    return {
+        "xyz": take([col["x"], col["y"], col["z"]]),
+        "features_dc": take([col["f_dc_0"], col["f_dc_1"], col["f_dc_2"]]).reshape(n, 3, 1).transpose(1, 2).contiguous(),
+        "features_rest": take(rest).reshape(n, 3, len(rest) // 3).transpose(1, 2).contiguous(),
+        "opacity": take([col["opacity"]]),
+        "scaling": take(numbered("scale_")),
+        "rotation": take(numbered("rot_")),
+    }

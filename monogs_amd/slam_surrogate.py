@@ -387,7 +387,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     return result
 
 
-def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
+def evaluate(result, frames, dev, every: int = 1, monocular: bool = True, native: bool = False):
     """ATE RMSE over all tracked frames and over the keyframes (Sim(3)-aligned when `monocular`:
     the scale of a monocular map is free; SE(3)-aligned otherwise, eval_utils.py:26-44),
     PSNR of the final map rendered at the estimated poses of the non-keyframes, against each camera's own
@@ -401,6 +401,32 @@ def evaluate(result, frames, dev, every: int = 1, monocular: bool = True):
     gt_c = torch.stack([torch.linalg.inv(frames[i].T_gt.double())[:3, 3] for i in ids])
     path = float((gt_c[1:] - gt_c[:-1]).norm(dim=1).sum())
     bg = torch.zeros(3, device=dev)
+    if native:
+        # the same views through eval_native.NativeEvaluator: one enqueued call per view, one copy at the end.  psnr_db
+        # stays the PSNR over ALL elements, as below (psnr_all); ssim and - for a run with sensor depth - depth_l1_m
+        # (against the camera's gt_depth, or the frame's depth) come with it.
+        from .eval_native import NativeEvaluator
+        chosen = [i for i in ids[::every] if i not in result["kf_ids"]]
+        res = None
+        if chosen:
+            v0 = cams[chosen[0]]
+            ev = NativeEvaluator(gm, bg, int(v0.image_height), int(v0.image_width), dev, max_views=len(chosen))
+            ev.begin()
+            for i in chosen:
+                v = cams[i]
+                depth = None
+                if not monocular:
+                    depth = getattr(v, "gt_depth", None)
+                    if depth is None:
+                        depth = getattr(frames[i], "depth", None)
+                ev.score(v, v.original_image, gt_depth=depth, apply_exposure=True)
+            res = ev.finish()
+        out = {"ate_rmse_m": ate_all, "ate_rmse_keyframes_m": ate_kf, "path_length_m": path,
+               "psnr_db": res["mean_psnr_all"] if res else 0.0, "psnr_frames": len(chosen), "gaussians": len(gm),
+               "ssim": res["mean_ssim"] if res else float("nan")}
+        if res and res["mean_depth_l1"] is not None:
+            out["depth_l1_m"] = res["mean_depth_l1"]
+        return out
     ps = []
     with torch.no_grad():
         for i in ids[::every]:
