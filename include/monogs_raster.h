@@ -1328,6 +1328,105 @@ int32_t mgs_tracking_iteration_gauss_newton_rgbd(const mgs_tracking_gn_args* arg
  * exposure, lm_state nor best is touched (the lm block may be zero).  depth may be NULL (monocular). */
 int32_t mgs_normal_equations(const mgs_tracking_gn_args* args, const mgs_tracking_depth_args* depth, void* stream);
 
+/* ---- headless viewer ("Headless viewer") -------------------------------------------------------------
+ * The last step from the forward's float planes to a finished uint8 [H,W,3] frame, on the device: what the reference's
+ * GUI does on the host with NumPy, imgviz, Open3D and OpenGL (gui/slam_gui.py:544-653, gui/gui_utils.py:24-66,
+ * gui/gl_render/shaders/gau_frag.glsl:20-35).  Four entry points, all stream-ordered and without a host read. */
+
+/* (a) float planes -> interleaved uint8.
+ *   MGS_VIEW_RGB      out = (uint8)(clamp(x, 0, 1) * 255), truncated (slam_gui.py:644-651); src is [3,H,W]
+ *   MGS_VIEW_DEPTH    t = (d - 0.1) / (max - 0.1), out = lut[index(t)]; src is [1,H,W]            (:578-588)
+ *   MGS_VIEW_OPACITY  t = o / max, out = lut[index(t)]                                            (:590-600)
+ * index(t) = min(255, (int)(clamp(t, 0, 1) * 256)).  max is the largest non-negative value of the plane (NaNs are
+ * passed over), found by a launch of its own into `scratch`; the subtraction and the division are single correctly
+ * rounded fp32 operations.  A NaN pixel is black; max <= lo gives t = 0 everywhere.  `lut` is the 256 x 3 colour map
+ * (monogs_amd.viewer.JET_LUT), kept in LDS.  `out` must be 4-byte aligned; H * W * 3 must stay below 2^31. */
+#define MGS_VIEW_RGB 0
+#define MGS_VIEW_DEPTH 1
+#define MGS_VIEW_OPACITY 2
+typedef struct mgs_view_compose_args {
+  int32_t width, height;
+  int32_t mode;
+  int32_t reserved0;
+  const float* src;        /* [3,H,W] (MGS_VIEW_RGB) or [1,H,W] */
+  const uint8_t* lut;      /* [256,3]; may be NULL for MGS_VIEW_RGB */
+  uint8_t* out;            /* [H,W,3] */
+  void* scratch;           /* mgs_view_compose_scratch_bytes() bytes, no initial state; may be NULL for MGS_VIEW_RGB */
+} mgs_view_compose_args;
+
+int32_t mgs_view_compose_args_size(void);
+uint64_t mgs_view_compose_scratch_bytes(void);
+int32_t mgs_view_compose(const mgs_view_compose_args* args, void* stream);
+
+/* (b) the ellipsoid shader: gau_frag.glsl:20-35 with render_mod -3 (flat ball) and -4 (Gaussian ball) on THIS
+ * rasteriser's projection and tile lists.  alpha = min(0.99, opacity * exp(power)) is made binary against a threshold
+ * (0.22 / 0.4; `power > 0` and `alpha < 1/255` skip the splat first) and a pixel shows the NEAREST splat with alpha = 1:
+ * hit_color = rgb (flat) or rgb * exp(power) (Gaussian), hit_depth = the splat's depth; without a hit the background
+ * and 0.  Launch sequence: mgs_raster_forward_project, the pair emission and per-tile sort of
+ * mgs_raster_forward_blend, then one forward-only walk of the sorted lists (no blend: fwd.out_color / out_depth /
+ * out_opacity must be given as for the forward but are not written, fwd.n_touched is left zero).  Complete iff D <= fwd.shape.pair_capacity, as the blend. */
+#define MGS_VIEW_FLAT_BALL 3
+#define MGS_VIEW_GAUSSIAN_BALL 4
+typedef struct mgs_view_ellipsoid_args {
+  mgs_forward_args fwd;    /* the forward's argument block and workspaces */
+  int32_t mode;            /* MGS_VIEW_FLAT_BALL or MGS_VIEW_GAUSSIAN_BALL */
+  int32_t reserved0;
+  float* hit_color;        /* [3,H,W] */
+  float* hit_depth;        /* [1,H,W] */
+} mgs_view_ellipsoid_args;
+
+int32_t mgs_view_ellipsoid_args_size(void);
+int32_t mgs_view_ellipsoid(const mgs_view_ellipsoid_args* args, void* stream);
+
+/* (c) the time shader (slam_gui.py:550-558): out[n,k,:] = 0.1 * features[n,k,:] + 0.9 * lut[index(t_n)] / 255 for every
+ * coefficient row k, t_n = (kf_ids[n] - id_min) / (id_max - id_min) (integer difference, one fp32 division; 0 when all
+ * ids are equal), index() as in (a).  id_min / id_max are found by a launch of its own; `features` is not modified. */
+typedef struct mgs_view_time_colors_args {
+  int32_t num_gaussians;   /* N >= 1 */
+  int32_t sh_coeffs;       /* K >= 1 */
+  const float* features;   /* [N,K,3] */
+  const int32_t* kf_ids;   /* [N] */
+  const uint8_t* lut;      /* [256,3] */
+  float* out;              /* [N,K,3] caller's scratch */
+  void* scratch;           /* mgs_view_time_colors_scratch_bytes() bytes, no initial state */
+} mgs_view_time_colors_args;
+
+int32_t mgs_view_time_colors_args_size(void);
+uint64_t mgs_view_time_colors_scratch_bytes(void);
+int32_t mgs_view_time_colors(const mgs_view_time_colors_args* args, void* stream);
+
+/* (d) frusta and free segments as 1-pixel lines over the frame, no depth test.
+ * Segments, in index order: eight per pose (gui_utils.py:52-66: points (0,0,0), (1,-.5,2), (-1,-.5,2), (1,.5,2),
+ * (-1,.5,2) times frustum_size in the pose's camera frame; lines 0-1 0-2 0-3 0-4 1-2 1-3 2-4 3-4), then the free ones.
+ * Step 1 (fp32): world -> view space with T_view, clip at z = near_z, project x = fx X / Z + cx, y = fy Y / Z + cy,
+ * clip to the guard rectangle [-W/2, 3W/2] x [-H/2, 3H/2], store round(16 x), round(16 y) and a valid flag in
+ * `endpoints` ([S,5] int32: x0, y0, x1, y1, valid; S = 8 num_poses + num_free).  A segment wholly behind the near plane
+ * or outside the rectangle is invalid and draws nothing.
+ * Step 2 (integers only): n = ceil(max(|dx|, |dy|) / 16) steps; pixel k = 0..n is at
+ * ((x0 + floor((2 dx k + n) / (2 n)) + 8) >> 4, likewise y), bounds-tested; n <= 2 max(W, H).  Where segments overlap
+ * the pixel takes the colour of the HIGHEST segment index (an int32 owner map in `scratch`, atomicMax, then a second
+ * walk that writes the owners' colours): the frame does not depend on the order of execution. */
+typedef struct mgs_view_overlay_args {
+  int32_t width, height;
+  int32_t num_poses;          /* K >= 0 */
+  int32_t num_free;           /* M >= 0 */
+  float fx, fy, cx, cy;
+  float frustum_size;
+  float near_z;               /* > 0 */
+  const float* T_view;        /* [4,4] row-major world -> camera of the viewing camera */
+  const float* poses;         /* [K,4,4] row-major camera -> world, or NULL when K == 0 */
+  const float* free_segments; /* [M,2,3] world-space end points, or NULL when M == 0 */
+  const uint8_t* pose_colors; /* [K,3] */
+  const uint8_t* free_colors; /* [M,3] */
+  int32_t* endpoints;         /* [S,5] out (caller-visible) */
+  uint8_t* frame;             /* [H,W,3] in / out */
+  void* scratch;              /* mgs_view_overlay_scratch_bytes(W, H) bytes, no initial state */
+} mgs_view_overlay_args;
+
+int32_t mgs_view_overlay_args_size(void);
+uint64_t mgs_view_overlay_scratch_bytes(int32_t width, int32_t height);   /* 0 for a bad size */
+int32_t mgs_view_overlay(const mgs_view_overlay_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

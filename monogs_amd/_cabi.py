@@ -37,6 +37,10 @@ EXPORTS = (
     "mgs_tracking_iteration_gauss_newton_rgbd", "mgs_normal_equations",
     "mgs_eval_score", "mgs_eval_score_partial_count", "mgs_eval_score_args_size", "mgs_eval_view_args_size",
     "mgs_eval_view",
+    "mgs_view_compose_args_size", "mgs_view_compose_scratch_bytes", "mgs_view_compose",
+    "mgs_view_ellipsoid_args_size", "mgs_view_ellipsoid",
+    "mgs_view_time_colors_args_size", "mgs_view_time_colors_scratch_bytes", "mgs_view_time_colors",
+    "mgs_view_overlay_args_size", "mgs_view_overlay_scratch_bytes", "mgs_view_overlay",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -323,6 +327,31 @@ class EvalViewArgs(C.Structure):
                 ("reserved0", C.c_int32)]
 
 
+VIEW_RGB, VIEW_DEPTH, VIEW_OPACITY, VIEW_FLAT_BALL, VIEW_GAUSSIAN_BALL = 0, 1, 2, 3, 4     # MGS_VIEW_*
+
+
+class ViewComposeArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "mode", "reserved0")]
+                + [(n, _fp) for n in ("src", "lut", "out", "scratch")])
+
+
+class ViewEllipsoidArgs(C.Structure):
+    _fields_ = [("fwd", ForwardArgs), ("mode", C.c_int32), ("reserved0", C.c_int32), ("hit_color", _fp),
+                ("hit_depth", _fp)]
+
+
+class ViewTimeColorsArgs(C.Structure):
+    _fields_ = ([("num_gaussians", C.c_int32), ("sh_coeffs", C.c_int32)]
+                + [(n, _fp) for n in ("features", "kf_ids", "lut", "out", "scratch")])
+
+
+class ViewOverlayArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "num_poses", "num_free")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "frustum_size", "near_z")]
+                + [(n, _fp) for n in ("T_view", "poses", "free_segments", "pose_colors", "free_colors", "endpoints",
+                                      "frame", "scratch")])
+
+
 _lib = None
 
 
@@ -492,6 +521,19 @@ def lib():
     L.mgs_eval_score.argtypes = [C.POINTER(EvalScoreArgs), C.c_void_p]
     L.mgs_eval_view.restype = C.c_int32
     L.mgs_eval_view.argtypes = [C.POINTER(EvalViewArgs), C.c_void_p]
+    for fn, cls in ((L.mgs_view_compose_args_size, ViewComposeArgs), (L.mgs_view_ellipsoid_args_size, ViewEllipsoidArgs),
+                    (L.mgs_view_time_colors_args_size, ViewTimeColorsArgs),
+                    (L.mgs_view_overlay_args_size, ViewOverlayArgs)):
+        fn.restype, fn.argtypes = C.c_int32, []
+        if fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    for fn in (L.mgs_view_compose_scratch_bytes, L.mgs_view_time_colors_scratch_bytes):
+        fn.restype, fn.argtypes = C.c_uint64, []
+    L.mgs_view_overlay_scratch_bytes.restype = C.c_uint64
+    L.mgs_view_overlay_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    for fn, cls in ((L.mgs_view_compose, ViewComposeArgs), (L.mgs_view_ellipsoid, ViewEllipsoidArgs),
+                    (L.mgs_view_time_colors, ViewTimeColorsArgs), (L.mgs_view_overlay, ViewOverlayArgs)):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

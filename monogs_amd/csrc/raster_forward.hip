@@ -1189,7 +1189,8 @@ int launch_forward_project(const KP& P, hipStream_t st) {
   return check_launch();
 }
 
-int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD) {
+// Pair emission and per-tile depth sort: the front of stage 2, which the viewer's first-hit walk (viewer.hip) shares.
+int launch_forward_sort(const KP& P, hipStream_t st) {
   // cursors restart at 0 on every call so a retry with a larger capacity is valid
   // (n_touched is zeroed by the emit pass of the LDS path)
   if (P.T <= kBinMaxTilesLds) {
@@ -1217,6 +1218,12 @@ int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD) {
     launch("tile_sort", k_tile_sort_reg<false>, dim3(P.T), dim3(256), st, P);
     if (P.big_pass) launch("tile_sort_big", k_tile_sort<4096, 1024, false, 1024>, dim3(min(P.T, 512)), dim3(1024), st, P);
   }
+  return check_launch();
+}
+
+int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD) {
+  const int rc = launch_forward_sort(P, st);
+  if (rc != MGS_OK) return rc;
 #ifdef MGS_FWD_BLOCKS
   constexpr int kFwdGridChunk = 64;
 #else

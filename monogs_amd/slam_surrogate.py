@@ -175,7 +175,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  use_first_order_best: bool = True, use_best_loss: bool = True, rgbd_tracking: bool = False,
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
                  native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
-                 stereo_matcher=None, second_order_exact: bool = False):
+                 stereo_matcher=None, second_order_exact: bool = False, viewer_every: int = 0,
+                 viewer_modes=("rgb",), viewer_follow: bool = True):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -208,7 +209,12 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     camera's image is the matcher's rectified left image, and from there the run is `sensor_depth=True`'s with that
     depth in the place of `frame.depth` - what the reference's stereo dataset hands its frontend.
     `second_order_exact` (slam_loops.second_order_exact reads it from a config): the second-order iterations are dense
-    Gauss-Newton steps (NativeTracker.enable_second_order(exact=True)) instead of sketched ones."""
+    Gauss-Newton steps (NativeTracker.enable_second_order(exact=True)) instead of sketched ones.
+    `viewer_every` = k > 0: after every k-th tracked frame (and its keyframe work), outside the timed sections, a
+    viewer.NativeViewer takes one frame per mode of `viewer_modes` of the map as it then is - from the follow-camera
+    behind the tracked pose (`viewer_follow`) or from the tracked camera itself - with the keyframe frusta, the current
+    camera and the trajectory so far drawn over it; the result then also holds `view_frames`:
+    {frame id: {mode: uint8 [H,W,3] device tensor}}.  Tracking and mapping never read anything the viewer writes."""
     if stereo_matcher is not None:
         if any(getattr(f, "image_right", None) is None for f in frames):
             raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
@@ -286,6 +292,27 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             t_prepare += time.perf_counter() - tp
         return v
 
+    view_frames, viewer = {}, None
+
+    def take_views(k):
+        """The viewer's frames of the map after frame k (viewer_every): outside the timed sections."""
+        nonlocal viewer
+        from .viewer import NativeViewer, follow_camera
+        if viewer is None or viewer.gaussians is not gm:        # (a monocular reset starts a fresh map)
+            viewer = NativeViewer(gm, bg, H, W, dev)
+        vp_k = cams[k]
+        vcam = follow_camera(vp_k.T, H, W, fovy, behind=True, device=dev) if viewer_follow else vp_k
+        c2w = {i: torch.linalg.inv(cams[i].T.detach()) for i in sorted(cams)}
+        overlay = dict(keyframes=torch.stack([c2w[i] for i in kf_ids]), current=c2w[k],
+                       trajectory=torch.stack([c2w[i][:3, 3] for i in sorted(c2w)]))
+        for _ in range(3):
+            shots = {m: viewer.frame(vcam, m, **overlay) for m in viewer_modes}
+            if viewer.check_capacity():
+                break
+        else:
+            raise RuntimeError("viewer: pair capacity still exceeded after growing the workspaces three times")
+        view_frames[k] = shots
+
     t_track = t_map = 0.0
     n_track_iters = n_map_iters = n_map_views = 0
     cams = {}
@@ -353,6 +380,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                 t_init += time.perf_counter() - t0
                 window, kf_ids, last_kf = [k], [k], k
                 windows.append(list(window))
+                if viewer_every > 0 and k % viewer_every == 0:
+                    take_views(k)
                 continue
         if create_kf:
             torch.cuda.synchronize()
@@ -375,6 +404,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             if log:
                 log(f"keyframe {k}: window {window}, {len(gm)} Gaussians, loss {float(mapper.last_loss):.4f}")
         windows.append(list(window))
+        if viewer_every > 0 and k % viewer_every == 0:
+            take_views(k)
     ok = mapper.check_capacity()
     result = {"cameras": cams, "kf_ids": kf_ids, "gaussians": gm, "mapper": mapper, "t_init": t_init,
               "t_track": t_track, "t_map": t_map, "n_track_iters": n_track_iters, "n_map_iters": n_map_iters,
@@ -384,6 +415,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         result["seed_records"] = seed_records
     if preparer is not None:
         result["t_prepare"] = t_prepare
+    if viewer_every > 0:
+        result["view_frames"] = view_frames
     return result
 
 
