@@ -1427,6 +1427,82 @@ int32_t mgs_view_overlay_args_size(void);
 uint64_t mgs_view_overlay_scratch_bytes(int32_t width, int32_t height);   /* 0 for a bad size */
 int32_t mgs_view_overlay(const mgs_view_overlay_args* args, void* stream);
 
+/* ---- mesh export ("Mesh export") -----------------------------------------------------------------------
+ * A dense lattice of nx x ny x nz sample points, point (i,j,k) at origin + (i,j,k) * voxel_size, i fastest; planes
+ * tsdf (initial 1), weight (initial 0) and color [3,nz,ny,nx] (initial 0), all fp32 and caller-owned: the library keeps
+ * no state.  Linear keys are 32-bit: 7 nx ny nz >= 2^31 gives MGS_ERR_UNSUPPORTED.
+ *
+ * (a) mgs_tsdf_integrate: ONE view, one launch, no host read.  Per lattice point, every operation a single fp32
+ * rounding, in this order:
+ *   p = origin + idx * vs per axis;  pc = ((R_0 px + R_1 py) + R_2 pz) + t  with the world-to-camera T
+ *   skip unless zc > z_near;  u = fx * (xc / zc) + cx, v likewise;  pixel = floor(u + 0.5), floor(v + 0.5), tested
+ *   against the image in float;  d = depth[v,u];  with `opacity`: skip if o < min_opacity, and with `normalize`
+ *   d = d / o;  skip unless d > depth_min and d <= depth_max;  sdf = d - zc;  skip if sdf < -trunc;
+ *   tn = min(1, sdf / trunc);  W' = W + weight;  D' = (W * D + weight * tn) / W';  with `image` each colour channel
+ *   C' = (W * C + weight * image[c,v,u]) / W';  stored weight min(W', max_weight).
+ * Bricks of 32 x 8 x 4 points whose corners all lie beyond one plane of the view volume are left untouched; the
+ * result is the un-culled one bit for bit. */
+typedef struct mgs_tsdf_integrate_args {
+  int32_t nx, ny, nz;
+  int32_t width, height;
+  int32_t normalize;         /* d = d / o (needs `opacity`) */
+  float origin[3];
+  float voxel_size;          /* > 0 */
+  float trunc;               /* > 0 */
+  float fx, fy, cx, cy;      /* fx, fy > 0 */
+  float z_near, depth_min, depth_max;
+  float min_opacity;
+  float weight;              /* of this view, > 0 */
+  float max_weight;          /* > 0 */
+  int32_t reserved0;
+  const float* T;            /* [4,4] row-major world -> camera, on the device */
+  const float* depth;        /* [H,W] */
+  const float* opacity;      /* [H,W] or NULL */
+  const float* image;        /* [3,H,W] or NULL */
+  float* tsdf;               /* [nz,ny,nx] */
+  float* wsum;               /* [nz,ny,nx] the weight plane */
+  float* color;              /* [3,nz,ny,nx]; may be NULL without `image` */
+} mgs_tsdf_integrate_args;
+
+int32_t mgs_tsdf_integrate_args_size(void);
+int32_t mgs_tsdf_integrate(const mgs_tsdf_integrate_args* args, void* stream);
+
+/* (b) surface extraction: marching tetrahedra over the Kuhn decomposition (six tetrahedra per cell, one per
+ * permutation (a,b,c) of the axes: v0 = (0,0,0), v1 = v0 + e_a, v2 = v1 + e_b, v3 = (1,1,1)).  A cell is valid when
+ * its eight corners have weight >= min_weight; a corner is inside when tsdf < 0.  A lattice point owns the 7 edges to
+ * its neighbours at (1,0,0) (0,1,0) (0,0,1) (1,1,0) (1,0,1) (0,1,1) (1,1,1) (slots 0..6), key = 7 * linear + slot; an
+ * edge carries a vertex iff its end points differ in sign and a valid cell contains it.  With a the owner and b the
+ * other end: f = ta / (ta - tb), position pa + f * (pb - pa) per axis (single roundings), the colour likewise.
+ * Vertices come out in ascending key order, faces as int32 triples wound so that (v1 - v0) x (v2 - v0) points to the
+ * outside corners, ordered by cell, tetrahedron, triangle: two calls give the same bytes.
+ *   mgs_tsdf_mesh_count   classify + scan into `scratch`; counts[0] = V, counts[1] = F (device; saturated at 2^31 - 1)
+ *   mgs_tsdf_mesh_emit    after the caller has read counts: writes num_verts vertices / colours and num_faces faces
+ *                         (never more: the counts bound every store).  num_verts = num_faces = 0 launches nothing.
+ * `scratch` (mgs_tsdf_mesh_scratch_bytes, 0 for a bad size; no initial state) carries the classification from count to
+ * emit; the planes must not change in between. */
+typedef struct mgs_tsdf_mesh_args {
+  int32_t nx, ny, nz;
+  int32_t reserved0;
+  float origin[3];
+  float voxel_size;
+  float min_weight;
+  int32_t reserved1;
+  const float* tsdf;
+  const float* weight;
+  const float* color;        /* [3,nz,ny,nx] or NULL (then `colors` is not written) */
+  void* scratch;
+  int32_t* counts;           /* [2] device (count only) */
+  float* verts;              /* [num_verts,3] (emit only) */
+  int32_t* faces;            /* [num_faces,3] (emit only) */
+  float* colors;             /* [num_verts,3] or NULL (emit only) */
+  int32_t num_verts, num_faces;   /* as read from counts (emit only) */
+} mgs_tsdf_mesh_args;
+
+int32_t mgs_tsdf_mesh_args_size(void);
+uint64_t mgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
+int32_t mgs_tsdf_mesh_count(const mgs_tsdf_mesh_args* args, void* stream);
+int32_t mgs_tsdf_mesh_emit(const mgs_tsdf_mesh_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

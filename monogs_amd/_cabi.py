@@ -41,6 +41,8 @@ EXPORTS = (
     "mgs_view_ellipsoid_args_size", "mgs_view_ellipsoid",
     "mgs_view_time_colors_args_size", "mgs_view_time_colors_scratch_bytes", "mgs_view_time_colors",
     "mgs_view_overlay_args_size", "mgs_view_overlay_scratch_bytes", "mgs_view_overlay",
+    "mgs_tsdf_integrate_args_size", "mgs_tsdf_integrate", "mgs_tsdf_mesh_args_size", "mgs_tsdf_mesh_scratch_bytes",
+    "mgs_tsdf_mesh_count", "mgs_tsdf_mesh_emit",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -352,6 +354,25 @@ class ViewOverlayArgs(C.Structure):
                                       "frame", "scratch")])
 
 
+TSDF_MAX_POINTS = (2 ** 31 - 1) // 7     # 7 nx ny nz < 2^31: the edge keys of the extraction are 32-bit
+
+
+class TsdfIntegrateArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("nx", "ny", "nz", "width", "height", "normalize")]
+                + [("origin", C.c_float * 3)]
+                + [(n, C.c_float) for n in ("voxel_size", "trunc", "fx", "fy", "cx", "cy", "z_near", "depth_min",
+                                            "depth_max", "min_opacity", "weight", "max_weight")]
+                + [("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("T", "depth", "opacity", "image", "tsdf", "wsum", "color")])
+
+
+class TsdfMeshArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("nx", "ny", "nz", "reserved0")] + [("origin", C.c_float * 3)]
+                + [("voxel_size", C.c_float), ("min_weight", C.c_float), ("reserved1", C.c_int32)]
+                + [(n, _fp) for n in ("tsdf", "weight", "color", "scratch", "counts", "verts", "faces", "colors")]
+                + [("num_verts", C.c_int32), ("num_faces", C.c_int32)])
+
+
 _lib = None
 
 
@@ -534,6 +555,15 @@ def lib():
     for fn, cls in ((L.mgs_view_compose, ViewComposeArgs), (L.mgs_view_ellipsoid, ViewEllipsoidArgs),
                     (L.mgs_view_time_colors, ViewTimeColorsArgs), (L.mgs_view_overlay, ViewOverlayArgs)):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
+    for fn, cls in ((L.mgs_tsdf_integrate_args_size, TsdfIntegrateArgs), (L.mgs_tsdf_mesh_args_size, TsdfMeshArgs)):
+        fn.restype, fn.argtypes = C.c_int32, []
+        if fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    L.mgs_tsdf_mesh_scratch_bytes.restype = C.c_uint64
+    L.mgs_tsdf_mesh_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mgs_tsdf_integrate.restype, L.mgs_tsdf_integrate.argtypes = C.c_int32, [C.POINTER(TsdfIntegrateArgs), C.c_void_p]
+    for fn in (L.mgs_tsdf_mesh_count, L.mgs_tsdf_mesh_emit):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(TsdfMeshArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -278,3 +278,27 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
     path = os.path.join(name, sub, "point_cloud.ply")
     gaussians.save_ply(path)
     return path
+
+
+def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
+              voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, **fuse_kw):
+    """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
+    save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
+    from its own rendered depth at `cameras` (tsdf.fuse_map; `background` defaults to black).  Returns the path, or
+    None without a name."""
+    from . import tsdf
+    from .ply_io import write_mesh_ply
+    if name is None:
+        return None
+    vol = gaussians_or_volume
+    if not isinstance(vol, tsdf.TSDFVolume):
+        if cameras is None:
+            raise ValueError("save_mesh: a Gaussian model needs the cameras to fuse from")
+        if background is None:
+            background = torch.zeros(3, device=vol.get_xyz.device)
+        vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
+    verts, faces, colors = vol.extract_mesh(min_weight)
+    sub = "point_cloud/final" if final else "point_cloud/iteration_{}".format(str(iteration))
+    path = os.path.join(name, sub, "mesh.ply")
+    write_mesh_ply(path, verts, faces, colors)
+    return path

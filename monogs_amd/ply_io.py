@@ -9,6 +9,9 @@ f_dc and f_rest are stored channel-major: the [N,K,3] parameter is written as tr
 is coefficient j % (K - 1) of channel j // (K - 1).  Every value is the RAW parameter (log scale, opacity logit,
 un-normalised quaternion).  An isotropic model has the single column scale_0.
 
+write_mesh_ply / read_mesh_ply hold the triangle mesh of monogs_amd.tsdf (DESIGN.md "Mesh export"): vertices
+x y z (fp32) red green blue (uchar), faces `property list uchar int vertex_indices`, binary little-endian.
+
 Free functions on plain tensors, no GPU needed.  `plyfile` is not used: the writer emits the bytes above itself, so the
 agreement with a file plyfile would write is by the PLY specification, not by comparison."""
 from __future__ import annotations
@@ -53,6 +56,87 @@ def write_gaussian_ply(path: str, xyz, features_dc, features_rest, opacity, scal
     with open(path, "wb") as fh:
         fh.write(("\n".join(header) + "\n").encode("ascii"))
         fh.write(rows.tobytes())
+
+
+MESH_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+MESH_FACE_DTYPE = np.dtype([("count", "u1"), ("vertex_indices", "<i4", (3,))])
+
+
+def mesh_ply_header(num_verts: int, num_faces: int) -> str:
+    return ("ply\nformat binary_little_endian 1.0\n"
+            f"element vertex {num_verts}\n"
+            "property float x\nproperty float y\nproperty float z\n"
+            "property uchar red\nproperty uchar green\nproperty uchar blue\n"
+            f"element face {num_faces}\n"
+            "property list uchar int vertex_indices\n"
+            "end_header\n")
+
+
+def quantise_colors(colors) -> np.ndarray:
+    """fp32 colours in [0, 1] -> uint8, rounded to nearest (NaN gives 0)."""
+    c = torch.as_tensor(colors).detach().to(torch.float32)
+    c = torch.nan_to_num(c, nan=0.0).clamp(0.0, 1.0)
+    return torch.floor(c * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
+
+
+def write_mesh_ply(path: str, verts, faces, colors=None) -> None:
+    """A triangle mesh as binary little-endian PLY: per vertex x y z (fp32) and red green blue (uint8; fp32 colours are
+    quantised by quantise_colors, None is white), per face a uchar count of 3 and three int32 vertex indices.  The
+    tensors are copied to the host once each."""
+    v = torch.as_tensor(verts).detach().to(torch.float32).cpu().numpy().reshape(-1, 3)
+    f = torch.as_tensor(faces).detach().to(torch.int32).cpu().numpy().reshape(-1, 3)
+    if colors is None:
+        c = np.full((v.shape[0], 3), 255, np.uint8)
+    else:
+        c = torch.as_tensor(colors)
+        c = c.detach().cpu().numpy() if c.dtype == torch.uint8 else quantise_colors(c)
+        c = c.reshape(-1, 3)
+    if c.shape[0] != v.shape[0]:
+        raise ValueError(f"{c.shape[0]} colours for {v.shape[0]} vertices")
+    if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
+        raise ValueError("face index out of range")
+    vr = np.empty(v.shape[0], MESH_VERTEX_DTYPE)
+    vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
+    vr["red"], vr["green"], vr["blue"] = c[:, 0], c[:, 1], c[:, 2]
+    fr = np.empty(f.shape[0], MESH_FACE_DTYPE)
+    fr["count"] = 3
+    fr["vertex_indices"] = f
+    d = os.path.dirname(path)
+    if d:
+        os.makedirs(d, exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(mesh_ply_header(v.shape[0], f.shape[0]).encode("ascii"))
+        fh.write(vr.tobytes())
+        fh.write(fr.tobytes())
+
+
+def read_mesh_ply(path: str):
+    """The inverse of write_mesh_ply: (verts [V,3] f32, faces [F,3] i32, colors [V,3] uint8) as CPU tensors.  Only the
+    layout write_mesh_ply emits is read."""
+    with open(path, "rb") as fh:
+        blob = fh.read()
+    end = blob.find(b"end_header\n")
+    if not blob.startswith(b"ply\n") or end < 0:
+        raise ValueError(f"{path}: not a PLY file")
+    lines = blob[:end].decode("ascii").split("\n")
+    body = end + len(b"end_header\n")
+    counts = {ln.split()[1]: int(ln.split()[2]) for ln in lines if ln.startswith("element ")}
+    if "vertex" not in counts or "face" not in counts:
+        raise ValueError(f"{path}: a vertex and a face element are expected")
+    nv, nf = counts["vertex"], counts["face"]
+    if blob[:body].decode("ascii") != mesh_ply_header(nv, nf):
+        raise ValueError(f"{path}: not the layout write_mesh_ply emits")
+    need = nv * MESH_VERTEX_DTYPE.itemsize + nf * MESH_FACE_DTYPE.itemsize
+    if len(blob) - body < need:
+        raise ValueError(f"{path}: {need} bytes of data expected, file too short")
+    vr = np.frombuffer(blob, MESH_VERTEX_DTYPE, count=nv, offset=body)
+    fr = np.frombuffer(blob, MESH_FACE_DTYPE, count=nf, offset=body + nv * MESH_VERTEX_DTYPE.itemsize)
+    if nf and (fr["count"] != 3).any():
+        raise ValueError(f"{path}: only triangles are read")
+    verts = np.stack([vr["x"], vr["y"], vr["z"]], 1).astype(np.float32)
+    cols = np.stack([vr["red"], vr["green"], vr["blue"]], 1).astype(np.uint8)
+    return (torch.from_numpy(verts.reshape(nv, 3)), torch.from_numpy(fr["vertex_indices"].astype(np.int32).reshape(nf, 3)),
+            torch.from_numpy(cols.reshape(nv, 3)))
 
 
 def read_gaussian_ply(path: str) -> Dict[str, torch.Tensor]:

@@ -471,3 +471,28 @@ def evaluate(result, frames, dev, every: int = 1, monocular: bool = True, native
             ps.append(float(E.psnr(img.unsqueeze(0), v.original_image.unsqueeze(0))))
     return {"ate_rmse_m": ate_all, "ate_rmse_keyframes_m": ate_kf, "path_length_m": path,
             "psnr_db": sum(ps) / max(1, len(ps)), "psnr_frames": len(ps), "gaussians": len(gm)}
+
+
+def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_depth=None, margin: float = 0.1,
+                     min_weight: float = 1.0, **fuse_kw):
+    """The surface of a finished run: fuses every `every_keyframe`-th keyframe of a run_sequence `result` (its
+    "cameras", "kf_ids", "gaussians") into a tsdf.TSDFVolume sized from the map and extracts the mesh:
+    (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device.  By default each keyframe contributes the map's
+    own rendered depth at its estimated pose (tsdf.fuse_map); `sensor_depth` - a dict keyframe id -> depth [H,W] in
+    the units of the map - fuses measured (sensor or stereo) depth with the keyframe's image instead."""
+    from . import tsdf
+    gm = result["gaussians"]
+    ids = list(result["kf_ids"])[::max(1, int(every_keyframe))]
+    cams = [result["cameras"][k] for k in ids]
+    if sensor_depth is None:
+        bg = torch.zeros(3, device=gm.get_xyz.device)
+        vol = tsdf.fuse_map(gm, cams, bg, voxel_size, margin=margin, **fuse_kw)
+    else:
+        vol = tsdf.TSDFVolume.for_map(gm, voxel_size, margin, trunc=fuse_kw.get("trunc"),
+                                      max_weight=fuse_kw.get("max_weight", 64.0))
+        for k, cam in zip(ids, cams):
+            img = cam.original_image
+            img = img if torch.is_tensor(img) and img.dtype == torch.float32 and img.dim() == 3 else None
+            vol.integrate(sensor_depth[k], cam.T, cam.fx, cam.fy, cam.cx, cam.cy, image=img,
+                          depth_max=fuse_kw.get("depth_max", math.inf))
+    return vol.extract_mesh(min_weight)
