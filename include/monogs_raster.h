@@ -1427,6 +1427,47 @@ int32_t mgs_view_overlay_args_size(void);
 uint64_t mgs_view_overlay_scratch_bytes(int32_t width, int32_t height);   /* 0 for a bad size */
 int32_t mgs_view_overlay(const mgs_view_overlay_args* args, void* stream);
 
+/* ---- surface planes ("Surface planes") -----------------------------------------------------------------
+ * Both calls are stream-ordered and read nothing back.
+ *
+ * (a) mgs_surface_forward: mgs_raster_forward_project, mgs_raster_forward_blend (fwd.out_color / out_depth /
+ * out_opacity ARE written, exactly as by those two calls) and then one forward-only walk of the same sorted per-tile
+ * lists.  Per pixel, in sort order: a splat counts iff power <= 0 and alpha = min(0.99, opacity * exp(power)) >= 1/255
+ * (the blend's rules); T <- T * (1 - alpha) from T = 1; the MEDIAN splat is the first counting splat after which
+ * T <= 0.5.  median_depth = that splat's view depth, median_index = its Gaussian id; 0 and -1 where T never reaches one
+ * half (2DGS keeps the last splat there; this contract does not).  The blend's T < 1e-4 stop cannot come before the
+ * crossing (T > 0.5 in front of it and alpha <= 0.99 leave T >= 0.005), so the walk has no stop rule.  Complete iff
+ * D <= fwd.shape.pair_capacity, as the blend; fwd.bins and a pair capacity >= 1 are required. */
+typedef struct mgs_surface_args {
+  mgs_forward_args fwd;      /* as for the forward */
+  float* median_depth;       /* [1,H,W] */
+  int32_t* median_index;     /* [H,W] or NULL */
+} mgs_surface_args;
+
+int32_t mgs_surface_args_size(void);
+int32_t mgs_surface_forward(const mgs_surface_args* args, void* stream);
+
+/* (b) mgs_depth_normal: camera-frame unit normals of any depth plane (the median plane, the blend's depth / opacity,
+ * sensor depth), every operation a single correctly rounded fp32 operation.  A depth is valid iff d > 0 and finite.  A
+ * pixel has a normal iff it is not on the image border, its own depth d_c and its left, right, upper and lower
+ * neighbours' depths d_n are valid and |d_n - d_c| <= max_jump * d_c for all four; otherwise the normal is (0,0,0).
+ *   P(x,y) = (((x + pixel_center - cx) / fx) * d, ((y + pixel_center - cy) / fy) * d, d)
+ *   a = P(x+1,y) - P(x-1,y);  b = P(x,y+1) - P(x,y-1);  n = b x a, each component one difference of two products;
+ *   len = sqrt((nx^2 + ny^2) + nz^2);  normal = n / len per component, (0,0,0) when len is zero or not finite.
+ * A fronto-parallel plane gives exactly (0,0,-1): towards the camera.  pixel_center is 0.5 for this rasteriser's
+ * planes (its pixel coordinate is fx X / Z + cx - 0.5) and 0 for sensor planes. */
+typedef struct mgs_depth_normal_args {
+  int32_t width, height;
+  float fx, fy, cx, cy;      /* fx, fy > 0 */
+  float pixel_center;
+  float max_jump;            /* >= 0 */
+  const float* depth;        /* [H,W] */
+  float* normal;             /* [3,H,W] */
+} mgs_depth_normal_args;
+
+int32_t mgs_depth_normal_args_size(void);
+int32_t mgs_depth_normal(const mgs_depth_normal_args* args, void* stream);
+
 /* ---- mesh export ("Mesh export") -----------------------------------------------------------------------
  * A dense lattice of nx x ny x nz sample points, point (i,j,k) at origin + (i,j,k) * voxel_size, i fastest; planes
  * tsdf (initial 1), weight (initial 0) and color [3,nz,ny,nx] (initial 0), all fp32 and caller-owned: the library keeps

@@ -41,6 +41,7 @@ EXPORTS = (
     "mgs_view_ellipsoid_args_size", "mgs_view_ellipsoid",
     "mgs_view_time_colors_args_size", "mgs_view_time_colors_scratch_bytes", "mgs_view_time_colors",
     "mgs_view_overlay_args_size", "mgs_view_overlay_scratch_bytes", "mgs_view_overlay",
+    "mgs_surface_args_size", "mgs_surface_forward", "mgs_depth_normal_args_size", "mgs_depth_normal",
     "mgs_tsdf_integrate_args_size", "mgs_tsdf_integrate", "mgs_tsdf_mesh_args_size", "mgs_tsdf_mesh_scratch_bytes",
     "mgs_tsdf_mesh_count", "mgs_tsdf_mesh_emit",
 )
@@ -354,6 +355,16 @@ class ViewOverlayArgs(C.Structure):
                                       "frame", "scratch")])
 
 
+class SurfaceArgs(C.Structure):
+    _fields_ = [("fwd", ForwardArgs), ("median_depth", _fp), ("median_index", _fp)]
+
+
+class DepthNormalArgs(C.Structure):
+    _fields_ = ([("width", C.c_int32), ("height", C.c_int32)]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "pixel_center", "max_jump")]
+                + [("depth", _fp), ("normal", _fp)])
+
+
 TSDF_MAX_POINTS = (2 ** 31 - 1) // 7     # 7 nx ny nz < 2^31: the edge keys of the extraction are 32-bit
 
 
@@ -554,6 +565,12 @@ def lib():
     L.mgs_view_overlay_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     for fn, cls in ((L.mgs_view_compose, ViewComposeArgs), (L.mgs_view_ellipsoid, ViewEllipsoidArgs),
                     (L.mgs_view_time_colors, ViewTimeColorsArgs), (L.mgs_view_overlay, ViewOverlayArgs)):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
+    for size_fn, fn, cls in ((L.mgs_surface_args_size, L.mgs_surface_forward, SurfaceArgs),
+                             (L.mgs_depth_normal_args_size, L.mgs_depth_normal, DepthNormalArgs)):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
     for fn, cls in ((L.mgs_tsdf_integrate_args_size, TsdfIntegrateArgs), (L.mgs_tsdf_mesh_args_size, TsdfMeshArgs)):
         fn.restype, fn.argtypes = C.c_int32, []

@@ -31,6 +31,7 @@ int launch_forward_project(const KP& P, hipStream_t st);
 int launch_forward_blend(const KP& P, hipStream_t st, const KObjDepth* PD = nullptr);
 int launch_forward_sort(const KP& P, hipStream_t st);
 int launch_view_first_hit(const KP& P, int mode, float* hit_color, float* hit_depth, hipStream_t st);
+int launch_surface_median(const KP& P, float* median_depth, int* median_index, hipStream_t st);
 int launch_backward(const KP& P, const KB& B, hipStream_t st, bool skip_tau_reduce, const SketchFuse* fuse);
 int launch_normal_backward(const KP& P, const KB& B, hipStream_t st, const mgs_sketch_residual_args& A,
                            const mgs_tracking_depth_args* D, float* planes, float* l1_partial, float* partial);
@@ -201,6 +202,20 @@ int32_t mgs_view_ellipsoid(const mgs_view_ellipsoid_args* args, void* stream) {
   if ((rc = launch_forward_project(P, (hipStream_t)stream)) != MGS_OK) return rc;
   if ((rc = launch_forward_sort(P, (hipStream_t)stream)) != MGS_OK) return rc;
   return launch_view_first_hit(P, args->mode, args->hit_color, args->hit_depth, (hipStream_t)stream);
+}
+
+int32_t mgs_surface_args_size(void) { return (int32_t)sizeof(mgs_surface_args); }
+
+// Median depth (surface.hip): the ordinary forward, then one more walk of the lists it sorted.
+int32_t mgs_surface_forward(const mgs_surface_args* args, void* stream) {
+  if (!args || !args->median_depth) return MGS_ERR_BAD_ARGUMENT;
+  if (!args->fwd.bins || args->fwd.shape.pair_capacity < 1) return MGS_ERR_BAD_ARGUMENT;
+  KP P;
+  int rc = fill_kp(args->fwd, true, true, P);
+  if (rc != MGS_OK) return rc;
+  if ((rc = launch_forward_project(P, (hipStream_t)stream)) != MGS_OK) return rc;
+  if ((rc = launch_forward_blend(P, (hipStream_t)stream)) != MGS_OK) return rc;
+  return launch_surface_median(P, args->median_depth, args->median_index, (hipStream_t)stream);
 }
 
 // skip_tau_reduce: the caller sums tau_partial itself (*tau_partials / *num_partials are set)

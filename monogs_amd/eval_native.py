@@ -284,8 +284,8 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
-    from its own rendered depth at `cameras` (tsdf.fuse_map; `background` defaults to black).  Returns the path, or
-    None without a name."""
+    from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
+    depth instead of depth / opacity; `background` defaults to black).  Returns the path, or None without a name."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:

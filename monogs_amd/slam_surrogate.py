@@ -479,7 +479,8 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
     "cameras", "kf_ids", "gaussians") into a tsdf.TSDFVolume sized from the map and extracts the mesh:
     (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device.  By default each keyframe contributes the map's
     own rendered depth at its estimated pose (tsdf.fuse_map); `sensor_depth` - a dict keyframe id -> depth [H,W] in
-    the units of the map - fuses measured (sensor or stereo) depth with the keyframe's image instead."""
+    the units of the map - fuses measured (sensor or stereo) depth with the keyframe's image instead.  `fuse_kw` goes
+    to tsdf.fuse_map: depth_mode="median" fuses the median depth of every rendered view instead of depth / opacity."""
     from . import tsdf
     gm = result["gaussians"]
     ids = list(result["kf_ids"])[::max(1, int(every_keyframe))]

@@ -306,11 +306,40 @@ class TSDFVolume:
         _cabi.check(_cabi.lib().mgs_tsdf_integrate(C.byref(a), self._stream()), "mgs_tsdf_integrate")
         del keep
 
+    def _surface_viewer(self, gaussians, background, H, W):
+        """The NativeViewer of the median mode, kept on the volume per (H, W, map)."""
+        from .viewer import NativeViewer
+        key = (int(H), int(W), id(gaussians))
+        if getattr(self, "_viewer_key", None) != key:
+            self._viewer = NativeViewer(gaussians, background, H, W, self.dev)
+            self._viewer_key = key
+        self._viewer.bg = background.detach().to(self.dev, torch.float32).reshape(-1).contiguous()
+        return self._viewer
+
     def integrate_view(self, gaussians, camera, background, image=None, min_opacity=0.95, weight=1.0,
-                       depth_min=0.0, depth_max=math.inf, z_near=0.2):
-        """Renders the map at `camera` (ViewCamera: T, fx, fy, cx, cy) through the forward and integrates
-        depth / opacity where opacity >= min_opacity.  The colour is the rendered one unless `image` is given.
-        Returns the render package."""
+                       depth_min=0.0, depth_max=math.inf, z_near=0.2, depth_mode="mean"):
+        """Renders the map at `camera` (ViewCamera: T, fx, fy, cx, cy) through the forward and integrates it where
+        opacity >= min_opacity.  depth_mode "mean" fuses depth / opacity, the expected depth of the blend, and returns
+        the render package.  "median" fuses the median depth (viewer.NativeViewer.surface: the depth of the splat at
+        which the transmittance falls through one half), which does not bleed at silhouettes, and returns the
+        surface planes; the pair capacity is confirmed BEFORE the view is integrated (one host read per view, as
+        render() has; a view that exceeded it is rendered again, never integrated twice).  The colour is the rendered
+        one unless `image` is given."""
+        if depth_mode not in ("mean", "median"):
+            raise ValueError(f"depth_mode must be 'mean' or 'median', got {depth_mode!r}")
+        if depth_mode == "median":
+            vw = self._surface_viewer(gaussians, background, camera.image_height, camera.image_width)
+            with torch.no_grad():
+                planes = vw.surface(camera, normals=False)
+                if not vw.check_capacity():         # grown to 1.5 x the pairs this view holds: the second render is whole
+                    planes = vw.surface(camera, normals=False)
+                    if not vw.check_capacity():
+                        raise RuntimeError("TSDFVolume.integrate_view: the view exceeded the grown pair capacity")
+            self.integrate(planes["median_depth"], camera.T, camera.fx, camera.fy, camera.cx, camera.cy,
+                           image=planes["color"] if image is None else image, opacity=planes["opacity"],
+                           min_opacity=min_opacity, normalize=False, weight=weight, depth_min=depth_min,
+                           depth_max=depth_max, z_near=z_near)
+            return planes
         from .gaussian_renderer import render
         from .slam_loops import Pipe
         with torch.no_grad():
@@ -362,11 +391,13 @@ class TSDFVolume:
 
 def fuse_map(gaussians, cameras: Iterable, background, voxel_size: float, margin: float = 0.1, trunc=None,
              max_weight: float = 64.0, min_opacity: float = 0.95, depth_max: float = math.inf,
-             volume: Optional[TSDFVolume] = None) -> TSDFVolume:
-    """Fuses the map's own rendered depth at `cameras` into a volume sized from the map (or into `volume`)."""
+             volume: Optional[TSDFVolume] = None, depth_mode: str = "mean") -> TSDFVolume:
+    """Fuses the map's own rendered depth at `cameras` into a volume sized from the map (or into `volume`):
+    depth / opacity with depth_mode "mean", the median depth with "median" (TSDFVolume.integrate_view)."""
     vol = volume
     if vol is None:
         vol = TSDFVolume.for_map(gaussians, voxel_size, margin, trunc=trunc, max_weight=max_weight)
     for cam in cameras:
-        vol.integrate_view(gaussians, cam, background, min_opacity=min_opacity, depth_max=depth_max)
+        vol.integrate_view(gaussians, cam, background, min_opacity=min_opacity, depth_max=depth_max,
+                           depth_mode=depth_mode)
     return vol

@@ -3,7 +3,9 @@ gui/gl_render/shaders/gau_frag.glsl:20-35) as finished uint8 [H,W,3] frames, mad
 
   NativeViewer.frame(camera, mode)   rgb | depth | opacity | time | flat_ball | gaussian_ball, with the keyframe frusta,
                                      the current camera and the trajectory drawn over it; enqueues HIP kernels
-                                     (csrc/viewer.hip through the C ABI) and reads nothing back
+                                     (csrc/viewer.hip through the C ABI) and reads nothing back; also the two
+                                     SURFACE_MODES median_depth | normal
+  NativeViewer.surface(camera)       the forward's planes plus median depth / index and normals (csrc/surface.hip)
   follow_camera(T, ...)              the GUI's view_dir / view_dir_behind camera of a tracked pose
   view_frame_torch(...)              the mirror in plain torch: the same arithmetic for the colour maps, the time tint
                                      and the line stepping; brute-force searches for the ellipsoid shader and the blend
@@ -27,6 +29,7 @@ from . import _cabi
 from .synthetic import SH_C0, projection_matrix2
 
 MODES = ("rgb", "depth", "opacity", "time", "flat_ball", "gaussian_ball")
+SURFACE_MODES = ("median_depth", "normal")      # views of the surface planes (surface.py); frame() takes them too
 DEPTH_LO = 0.1                        # slam_gui.py:582-584 (min_value of the depth colour map)
 BALL_THRESHOLD = {"flat_ball": 0.22, "gaussian_ball": 0.4}      # gau_frag.glsl:30,33
 NEAR_Z = 0.01                         # near plane of the line overlay (the cameras' znear)
@@ -378,16 +381,34 @@ def blend_torch(proj, H: int, W: int, bg: torch.Tensor, rows_per_chunk: int = 8)
 
 def view_frame_torch(mode: str = "rgb", *, color=None, depth=None, opacity=None, hit_color=None, gaussians=None,
                      camera=None, background=None, scale_modifier: float = 1.0, keyframes=None, current=None,
-                     trajectory=None, frustum_size: float = 0.02, endpoints=None) -> torch.Tensor:
+                     trajectory=None, frustum_size: float = 0.02, endpoints=None, median_depth=None, normal=None,
+                     max_jump: float = 0.05) -> torch.Tensor:
     """The mirror of NativeViewer.frame.  Given the float planes of a forward (`color`, `depth`, `opacity`; `hit_color`
     for the two ball modes) it repeats the device's arithmetic byte for byte: compose_torch, then overlay_draw_torch on
     `endpoints` (the device's own [S,5] end points; without them they are projected here in fp64, which agrees with the
     device to within a unit).  Without planes it makes them from `gaussians` and `camera` by brute force (project_torch,
-    blend_torch / first_hit_torch, the time tint through time_colors_torch) - the CPU route."""
-    if mode not in MODES:
-        raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
+    blend_torch / first_hit_torch, the time tint through time_colors_torch) - the CPU route.  The two SURFACE_MODES take
+    `median_depth` (the jet composition of the depth mode) and `normal` (0.5 n + 0.5 as rgb; without it the normals of
+    `median_depth` through surface.depth_normal_torch, for which `camera` gives the intrinsics)."""
+    if mode not in MODES + SURFACE_MODES:
+        raise ValueError(f"mode must be one of {MODES + SURFACE_MODES}, got {mode!r}")
     ball = mode in BALL_THRESHOLD
     plane = {"rgb": color, "time": color, "depth": depth, "opacity": opacity}.get(mode, hit_color)
+    if mode in SURFACE_MODES:
+        from . import surface
+        if median_depth is None and (mode == "median_depth" or normal is None):
+            if gaussians is None or camera is None:
+                raise ValueError("view_frame_torch needs the surface planes or (gaussians, camera)")
+            proj = project_torch(gaussians, camera, scale_modifier)
+            median_depth = surface.median_depth_torch(proj, camera.image_height, camera.image_width)[0]
+        if mode == "normal":
+            if normal is None:
+                if camera is None:
+                    raise ValueError("view_frame_torch: the normals of a median plane need `camera`")
+                normal = surface.depth_normal_torch(median_depth, camera.fx, camera.fy, camera.cx, camera.cy, 0.5, max_jump)
+            plane = surface.normal_rgb_torch(normal)
+        else:
+            plane = median_depth
     if plane is None:
         if gaussians is None or camera is None:
             raise ValueError("view_frame_torch needs the forward's planes or (gaussians, camera)")
@@ -403,7 +424,7 @@ def view_frame_torch(mode: str = "rgb", *, color=None, depth=None, opacity=None,
         else:
             c, d, o = blend_torch(proj, H, W, bg)
             plane = {"rgb": c, "time": c, "depth": d, "opacity": o}[mode]
-    frame = compose_torch(plane, mode if mode in ("depth", "opacity") else "rgb")
+    frame = compose_torch(plane, {"depth": "depth", "median_depth": "depth", "opacity": "opacity"}.get(mode, "rgb"))
     if keyframes is None and current is None and trajectory is None:
         return frame
     poses, pcol, free, fcol = overlay_segments(keyframes, current, trajectory, frustum_size, device="cpu")
@@ -442,9 +463,10 @@ class NativeViewer:
     """Frames of one map on the device.  frame() activates the map as it is now (mgs_map_activate), runs the forward
     (or mgs_view_ellipsoid) at a fixed pair capacity, composes the chosen plane into a new uint8 [H,W,3] tensor and
     draws the overlay - all enqueued on the current stream, nothing read back.  The planes of the last call stay in
-    `color`, `depth`, `opacity`, `hit_color`, `hit_depth`, the overlay's end points in `endpoints` (tests compare the
-    mirror on them).  check_capacity() is the one synchronising call: True when no frame so far exceeded the pair
-    capacity; otherwise the capacity is grown for the frames to come and the affected frames have to be taken again."""
+    `color`, `depth`, `opacity`, `hit_color`, `hit_depth` (and, after surface(), `median_depth`, `median_index`,
+    `normal`), the overlay's end points in `endpoints` (tests compare the mirror on them).  check_capacity() is the one
+    synchronising call: True when no frame so far exceeded the pair capacity; otherwise the capacity is grown for the
+    frames to come and the affected frames have to be taken again."""
 
     def __init__(self, gaussians, background, H: int, W: int, device, capacity: Optional[int] = None,
                  capacity_margin: float = 1.5):
@@ -462,6 +484,7 @@ class NativeViewer:
         self.color, self.hit_color = torch.empty(3, H, W, device=dev), torch.empty(3, H, W, device=dev)
         self.depth, self.opacity = torch.empty(1, H, W, device=dev), torch.empty(1, H, W, device=dev)
         self.hit_depth = torch.empty(1, H, W, device=dev)
+        self.median_depth = self.median_index = self.normal = None      # made by the first surface()
         self.compose_scratch = torch.empty(int(L.mgs_view_compose_scratch_bytes()), dtype=torch.uint8, device=dev)
         self.time_scratch = torch.empty(int(L.mgs_view_time_colors_scratch_bytes()), dtype=torch.uint8, device=dev)
         self.owner = torch.empty(int(L.mgs_view_overlay_scratch_bytes(self.W, self.H)), dtype=torch.uint8, device=dev)
@@ -584,19 +607,19 @@ class NativeViewer:
         """One finished frame: uint8 [H,W,3] on the device.  `camera`: T (world -> camera), projection_matrix, FoVx,
         FoVy, image_height / image_width (and fx, fy, cx, cy for the overlay) - a ViewCamera, make_view_camera() or
         follow_camera().  keyframes [K,4,4] / current [4,4]: camera -> world poses; trajectory [M,3]: world points."""
-        if mode not in MODES:
-            raise ValueError(f"mode must be one of {MODES}, got {mode!r}")
-        if int(camera.image_height) != self.H or int(camera.image_width) != self.W:
-            raise ValueError(f"camera is {camera.image_height} x {camera.image_width}, viewer {self.H} x {self.W}")
+        if mode not in MODES + SURFACE_MODES:
+            raise ValueError(f"mode must be one of {MODES + SURFACE_MODES}, got {mode!r}")
         L = _cabi.lib()
-        shs = self._activate()
-        if mode == "time":
-            shs = self.time_colors(shs, self.gaussians.unique_kfIDs, self.tinted)
-        f32 = lambda t: t.detach().to(self.dev, torch.float32).contiguous()
-        T, proj = f32(camera.T), f32(camera.projection_matrix)
-        self._keep_cam = (T, proj)
-        _cabi.check(L.mgs_camera_from_pose(T.data_ptr(), proj.data_ptr(), self.view_m.data_ptr(), self.full_m.data_ptr(),
-                                           self._stream()), "mgs_camera_from_pose")
+        if mode in SURFACE_MODES:
+            self.surface(camera, normals=mode == "normal", scale_modifier=scale_modifier)
+            if mode == "normal":                     # 0.5 n + 0.5: an exact product and one rounding, as the mirror
+                out = self.compose(torch.add(torch.mul(self.normal, 0.5), 0.5), "rgb")
+            else:
+                out = self.compose(self.median_depth, "depth")
+            if keyframes is not None or current is not None or trajectory is not None:
+                self.overlay(out, camera, keyframes, current, trajectory, frustum_size)
+            return out
+        shs, T, proj = self._prepare(camera, mode)
         if mode in BALL_THRESHOLD:
             a = _cabi.ViewEllipsoidArgs()
             self._forward_args(a.fwd, camera, shs, scale_modifier, T, proj)
@@ -613,6 +636,58 @@ class NativeViewer:
             out = self.compose(plane, mode if mode in ("depth", "opacity") else "rgb")
         if keyframes is not None or current is not None or trajectory is not None:
             self.overlay(out, camera, keyframes, current, trajectory, frustum_size)
+        return out
+
+    def _prepare(self, camera, mode: str = "rgb"):
+        """Activates the map and makes the camera's matrices on the device: (shs, T, projection)."""
+        if int(camera.image_height) != self.H or int(camera.image_width) != self.W:
+            raise ValueError(f"camera is {camera.image_height} x {camera.image_width}, viewer {self.H} x {self.W}")
+        shs = self._activate()
+        if mode == "time":
+            shs = self.time_colors(shs, self.gaussians.unique_kfIDs, self.tinted)
+        f32 = lambda t: t.detach().to(self.dev, torch.float32).contiguous()
+        T, proj = f32(camera.T), f32(camera.projection_matrix)
+        self._keep_cam = (T, proj)
+        _cabi.check(_cabi.lib().mgs_camera_from_pose(T.data_ptr(), proj.data_ptr(), self.view_m.data_ptr(),
+                                                     self.full_m.data_ptr(), self._stream()), "mgs_camera_from_pose")
+        return shs, T, proj
+
+    def depth_normal(self, depth: torch.Tensor, fx, fy, cx, cy, pixel_center: float = 0.5, max_jump: float = 0.05,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """mgs_depth_normal of a contiguous fp32 depth plane of this viewer's size on the device: [3,H,W]."""
+        if depth.device != self.dev or depth.dtype != torch.float32 or not depth.is_contiguous() or \
+                depth.numel() != self.H * self.W:
+            raise ValueError(f"depth_normal: depth must be a contiguous fp32 plane of {self.H} x {self.W} on {self.dev}")
+        out = torch.empty(3, self.H, self.W, device=self.dev) if out is None else out
+        a = _cabi.DepthNormalArgs()
+        a.width, a.height = self.W, self.H
+        a.fx, a.fy, a.cx, a.cy = float(fx), float(fy), float(cx), float(cy)
+        a.pixel_center, a.max_jump = float(pixel_center), float(max_jump)
+        a.depth, a.normal = depth.data_ptr(), out.data_ptr()
+        _cabi.check(_cabi.lib().mgs_depth_normal(C.byref(a), self._stream()), "mgs_depth_normal")
+        return out
+
+    def surface(self, camera, normals: bool = True, max_jump: float = 0.05, scale_modifier: float = 1.0) -> dict:
+        """The surface planes of one view (mgs_surface_forward, then mgs_depth_normal on the median plane with this
+        rasteriser's pixel centre 0.5): `color`, `depth`, `opacity` exactly as frame("rgb") leaves them, `median_depth`
+        [1,H,W] (0 where the transmittance never falls to one half), `median_index` [H,W] int32 (-1 there) and, with
+        `normals`, `normal` [3,H,W] in the camera frame (needs the camera's fx, fy, cx, cy).  Enqueued on the current
+        stream, nothing read back; the planes stay on the viewer and are returned as a dict.  check_capacity() tells
+        afterwards whether the pair capacity held, as for frame()."""
+        shs, T, proj = self._prepare(camera)
+        if self.median_depth is None:
+            self.median_depth = torch.empty(1, self.H, self.W, device=self.dev)
+            self.median_index = torch.empty(self.H, self.W, dtype=torch.int32, device=self.dev)
+            self.normal = torch.empty(3, self.H, self.W, device=self.dev)
+        a = _cabi.SurfaceArgs()
+        self._forward_args(a.fwd, camera, shs, scale_modifier, T, proj)
+        a.median_depth, a.median_index = self.median_depth.data_ptr(), self.median_index.data_ptr()
+        _cabi.check(_cabi.lib().mgs_surface_forward(C.byref(a), self._stream()), "mgs_surface_forward")
+        out = {"color": self.color, "depth": self.depth, "opacity": self.opacity, "median_depth": self.median_depth,
+               "median_index": self.median_index}
+        if normals:
+            self.depth_normal(self.median_depth, camera.fx, camera.fy, camera.cx, camera.cy, 0.5, max_jump, self.normal)
+            out["normal"] = self.normal
         return out
 
     def check_capacity(self) -> bool:
