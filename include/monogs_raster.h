@@ -1544,6 +1544,51 @@ uint64_t mgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int32_t mgs_tsdf_mesh_count(const mgs_tsdf_mesh_args* args, void* stream);
 int32_t mgs_tsdf_mesh_emit(const mgs_tsdf_mesh_args* args, void* stream);
 
+/* ---- mesh clean-up ("Mesh clean-up") -------------------------------------------------------------------
+ * Connected components of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL),
+ * clusters kept by size, vertices / colours / faces compacted.  The NumPy mirror mesh_clean.clean_mesh_numpy is the
+ * contract; the device equals it bit for bit, and two calls give the same bytes.
+ *   Components   two vertices are connected when a face names both (connectivity through shared vertices).
+ *   Labels       the label of a vertex is the SMALLEST vertex index of its component; a vertex no face names is its
+ *                own label, with a cluster of 0 faces.
+ *   Cluster size its number of faces; a face belongs to the cluster of its first index.  Degenerate (a,a,b) and
+ *                duplicate faces are ordinary faces: they connect what they name and they count.
+ *   Kept         a cluster is kept iff faces >= max(min_faces, 1) and, with keep_largest >= 0, its rank in the order
+ *                (face count descending, label ascending) is < keep_largest.  keep_largest = -1, min_faces = 0 drops
+ *                only the unreferenced vertices.
+ *   Output       the kept vertices and colours in their original relative order, the kept faces in theirs, re-indexed.
+ *   Bad indices  a face with an index outside [0,V) connects nothing, is counted into counts[4], never emitted.
+ *   mgs_mesh_clean_count   label, count, select, flag and scan into `scratch`;
+ *                          counts = (V', F', clusters with >= 1 face, kept clusters, bad faces) on the device
+ *   mgs_mesh_clean_emit    after the caller has read counts: writes out_num_verts vertices / colours and out_num_faces
+ *                          faces (never more: the counts bound every store).  Both 0 launches nothing.
+ *   mgs_mesh_components    labels [V] only, under the same rule (uses `scratch`, `faces`, `labels`)
+ * `scratch` (mgs_mesh_clean_scratch_bytes; no initial state) carries the flags from count to emit; `faces` must not
+ * change in between.  A null struct, scratch, counts (count), a needed array that is null, a negative size, keep_largest
+ * < -1 or min_faces < 0: MGS_ERR_BAD_ARGUMENT.  3 V >= 2^31 or 3 F >= 2^31: MGS_ERR_UNSUPPORTED, and scratch_bytes is
+ * 0.  V = 0 or F = 0 is legal.  A refused call launches nothing and writes nothing. */
+typedef struct mgs_mesh_clean_args {
+  int32_t num_verts, num_faces;
+  int32_t keep_largest;      /* -1: no limit */
+  int32_t min_faces;         /* >= 0 */
+  const float* verts;        /* [V,3] (emit only) */
+  const int32_t* faces;      /* [F,3] */
+  const float* colors;       /* [V,3] or NULL (emit only; then `out_colors` is not written) */
+  void* scratch;
+  int32_t* counts;           /* [5] device (count only) */
+  int32_t* labels;           /* [V] device (mgs_mesh_components only) */
+  float* out_verts;          /* [out_num_verts,3] (emit only) */
+  int32_t* out_faces;        /* [out_num_faces,3] (emit only) */
+  float* out_colors;         /* [out_num_verts,3] (emit only, with `colors`) */
+  int32_t out_num_verts, out_num_faces;   /* as read from counts[0], counts[1] (emit only) */
+} mgs_mesh_clean_args;
+
+int32_t mgs_mesh_clean_args_size(void);
+uint64_t mgs_mesh_clean_scratch_bytes(int32_t num_verts, int32_t num_faces);
+int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* args, void* stream);
+int32_t mgs_mesh_clean_emit(const mgs_mesh_clean_args* args, void* stream);
+int32_t mgs_mesh_components(const mgs_mesh_clean_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

@@ -44,6 +44,8 @@ EXPORTS = (
     "mgs_surface_args_size", "mgs_surface_forward", "mgs_depth_normal_args_size", "mgs_depth_normal",
     "mgs_tsdf_integrate_args_size", "mgs_tsdf_integrate", "mgs_tsdf_mesh_args_size", "mgs_tsdf_mesh_scratch_bytes",
     "mgs_tsdf_mesh_count", "mgs_tsdf_mesh_emit",
+    "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
+    "mgs_mesh_components",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -384,6 +386,17 @@ class TsdfMeshArgs(C.Structure):
                 + [("num_verts", C.c_int32), ("num_faces", C.c_int32)])
 
 
+MESH_CLEAN_MAX_ITEMS = (2 ** 31 - 1) // 3     # 3 V, 3 F < 2^31: 32-bit element indices of the [n,3] arrays
+MESH_CLEAN_COUNTS = 5                         # V', F', clusters, kept clusters, bad faces
+
+
+class MeshCleanArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "keep_largest", "min_faces")]
+                + [(n, _fp) for n in ("verts", "faces", "colors", "scratch", "counts", "labels", "out_verts",
+                                      "out_faces", "out_colors")]
+                + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
+
+
 _lib = None
 
 
@@ -581,6 +594,13 @@ def lib():
     L.mgs_tsdf_integrate.restype, L.mgs_tsdf_integrate.argtypes = C.c_int32, [C.POINTER(TsdfIntegrateArgs), C.c_void_p]
     for fn in (L.mgs_tsdf_mesh_count, L.mgs_tsdf_mesh_emit):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(TsdfMeshArgs), C.c_void_p]
+    L.mgs_mesh_clean_args_size.restype, L.mgs_mesh_clean_args_size.argtypes = C.c_int32, []
+    if L.mgs_mesh_clean_args_size() != C.sizeof(MeshCleanArgs):
+        raise NativeLibraryError("MeshCleanArgs does not have the size of mgs_mesh_clean_args")
+    L.mgs_mesh_clean_scratch_bytes.restype = C.c_uint64
+    L.mgs_mesh_clean_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    for fn in (L.mgs_mesh_clean_count, L.mgs_mesh_clean_emit, L.mgs_mesh_components):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshCleanArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -281,11 +281,13 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
-              voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, **fuse_kw):
+              voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
-    depth instead of depth / opacity; `background` defaults to black).  Returns the path, or None without a name."""
+    depth instead of depth / opacity; `background` defaults to black).  `clean` - a dict of mesh_clean.clean_mesh
+    keyword arguments, e.g. dict(keep_largest=1) - drops the floaters before the file is written.  Returns the path, or
+    None without a name."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -297,8 +299,8 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         if background is None:
             background = torch.zeros(3, device=vol.get_xyz.device)
         vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
-    verts, faces, colors = vol.extract_mesh(min_weight)
-    sub = "point_cloud/final" if final else "point_cloud/iteration_{}".format(str(iteration))
+    verts, faces, colors = vol.extract_mesh(min_weight) if clean is None else vol.extract_mesh(min_weight, clean=clean)
+    sub ="point_cloud/final" if final else "point_cloud/iteration_{}".format(str(iteration))
     path = os.path.join(name, sub, "mesh.ply")
     write_mesh_ply(path, verts, faces, colors)
     return path

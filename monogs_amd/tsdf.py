@@ -368,9 +368,11 @@ class TSDFVolume:
         a.scratch, a.counts = self._scratch.data_ptr(), self._counts.data_ptr()
         return a
 
-    def extract_mesh(self, min_weight: float = 1.0):
+    def extract_mesh(self, min_weight: float = 1.0, clean=None):
         """(verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device; empty tensors when nothing crosses.
-        One host read, of (V, F), between the scan and the emission."""
+        One host read, of (V, F), between the scan and the emission.  `clean` - a dict of mesh_clean.clean_mesh keyword
+        arguments, e.g. dict(keep_largest=1) or dict(min_faces=50) - drops the floaters from the extracted mesh (one
+        more host read); None leaves it as extracted."""
         L = _cabi.lib()
         a = self._mesh_args(min_weight)
         _cabi.check(L.mgs_tsdf_mesh_count(C.byref(a), self._stream()), "mgs_tsdf_mesh_count")
@@ -386,6 +388,9 @@ class TSDFVolume:
         if F:
             a.faces = faces.data_ptr()
         _cabi.check(L.mgs_tsdf_mesh_emit(C.byref(a), self._stream()), "mgs_tsdf_mesh_emit")
+        if clean is not None:
+            from .mesh_clean import clean_mesh
+            verts, faces, colors, _ = clean_mesh(verts, faces, colors, **clean)
         return verts, faces, colors
 
 
