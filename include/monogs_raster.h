@@ -1589,6 +1589,92 @@ int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* args, void* stream);
 int32_t mgs_mesh_clean_emit(const mgs_mesh_clean_args* args, void* stream);
 int32_t mgs_mesh_components(const mgs_mesh_clean_args* args, void* stream);
 
+/* ---- mesh evaluation ("Mesh evaluation") ---------------------------------------------------------------
+ * The geometry block of a reconstruction benchmark - accuracy, completion, precision / recall / F-score, Chamfer - from
+ * points sampled on two surfaces and their nearest distances in both directions.  Three stages, each with a mirror in
+ * monogs_amd/mesh_eval.py that defines it; the library keeps no state between calls.
+ *
+ * mgs_surface_sample   `num_samples` points uniform on the surface of (verts [V,3] f32, faces [F,3] i32).  Mirror:
+ *   sample_surface_numpy, equal bit for bit.
+ *     weight   n = (b - a) x (c - a), every product and difference rounded once; A = sqrt(nx^2 + ny^2 + nz^2), the sum
+ *              left to right, the root correctly rounded; E = the binary exponent of the largest finite A (an integer
+ *              maximum over bit patterns); q = uint32(trunc(A * 2^(30 - E))) < 2^31.  Non-finite A, or an index
+ *              outside [0,V) (counted as bad): q = 0.
+ *     CDF      C = inclusive prefix sum of q in uint64, T its total: integers, so exact in any order.
+ *     words    (x,y,z,w) = row j of `randoms` [n,4] u32 when given, else Philox-4x32-10 of counter (j, 0, 2, 0) keyed by
+ *              the halves of `seed`.
+ *     sample   t = (x | y << 32) mod T; face = the smallest f with C[f] > t; k1 = z >> 8, k2 = w >> 8, both replaced by
+ *              2^24 - k when k1 + k2 > 2^24; u = k * 2^-24; p = (a + u1 (b - a)) + u2 (c - a), every step rounded once.
+ *     T = 0    (or F = 0): every face_index -1, every point NaN, record[0] = 1.
+ *   record [MGS_SAMPLE_RECORD_INTS] i32 on the device: {T == 0, bad faces, low and high word of T}.
+ *
+ * mgs_nearest_distance   for every query the exact nearest of `ref`: d2 = min_r ((dx dx + dy dy) + dz dz), dx = q.x - r.x,
+ *   every step rounded once; index = the smallest r that attains it ((d2, r) compared lexicographically).  A non-finite
+ *   reference point is never a neighbour; a non-finite query, or no finite reference point, gives (inf, -1).  Mirror:
+ *   nearest_distance_torch (brute force), equal bit for bit.  The search runs over a uniform grid built on the device
+ *   (at most MGS_NEAREST_MAX_CELLS cells, at most MGS_NEAREST_MAX_DIM per axis); cell_size > 0 overrides the chosen
+ *   cell size and is raised until the grid fits the same caps.
+ *
+ * mgs_mesh_eval_stats    one direction (0: pred -> gt, 1: gt -> pred) of d2 [num] into per-workgroup partials in `scratch`:
+ *   over the finite d = sqrt(d2) their number, the number with d < threshold, the largest (integer maximum on the bit
+ *   pattern) and the fp64 sum.  No float atomics.
+ * mgs_mesh_eval_finish   after both directions: ONE workgroup adds the partials in a fixed order into record
+ *   [MGS_MESH_EVAL_RECORD_DOUBLES] f64 on the device: {n finite, n below, max d, sum d} of direction 0, of direction 1,
+ *   then {T == 0, bad faces} of sample_record[0] and of sample_record[1] (0 where the pointer is NULL).
+ *
+ * Every scratch (the *_scratch_bytes functions; no initial state) is sized from the host's numbers alone.  A null
+ * struct, scratch or needed array, a negative size, a direction outside {0, 1}, a negative or NaN cell_size or
+ * threshold: MGS_ERR_BAD_ARGUMENT.  3 V, 3 F, 3 n, 3 P or 3 Q >= 2^31: MGS_ERR_UNSUPPORTED, and scratch_bytes is 0.
+ * Sizes of 0 are legal.  A refused call launches nothing and writes nothing. */
+#define MGS_SAMPLE_RECORD_INTS 4
+#define MGS_NEAREST_MAX_CELLS (1 << 21)
+#define MGS_NEAREST_MAX_DIM 1024
+#define MGS_MESH_EVAL_RECORD_DOUBLES 12
+
+typedef struct mgs_surface_sample_args {
+  int32_t num_verts, num_faces, num_samples, reserved0;
+  uint64_t seed;
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3] */
+  const uint32_t* randoms;   /* [n,4] or NULL: replayed instead of the generator */
+  void* scratch;             /* mgs_surface_sample_scratch_bytes(num_faces) */
+  float* points;             /* [n,3] out */
+  int32_t* face_index;       /* [n] out */
+  int32_t* record;           /* [MGS_SAMPLE_RECORD_INTS] device out */
+} mgs_surface_sample_args;
+
+typedef struct mgs_nearest_args {
+  int32_t num_query, num_ref;
+  float cell_size;           /* 0: chosen on the device */
+  int32_t reserved0;
+  const float* query;        /* [P,3] */
+  const float* ref;          /* [Q,3] */
+  void* scratch;             /* mgs_nearest_scratch_bytes(num_ref) */
+  float* d2;                 /* [P] out */
+  int32_t* index;            /* [P] out */
+} mgs_nearest_args;
+
+typedef struct mgs_mesh_eval_args {
+  int32_t num, direction;
+  float threshold;
+  int32_t reserved0;
+  const float* d2;                   /* [num] (stats only) */
+  void* scratch;                     /* mgs_mesh_eval_scratch_bytes() */
+  double* record;                    /* [MGS_MESH_EVAL_RECORD_DOUBLES] device (finish only) */
+  const int32_t* sample_record[2];   /* device records of the two samplings, or NULL (finish only) */
+} mgs_mesh_eval_args;
+
+int32_t mgs_surface_sample_args_size(void);
+uint64_t mgs_surface_sample_scratch_bytes(int32_t num_faces);
+int32_t mgs_surface_sample(const mgs_surface_sample_args* args, void* stream);
+int32_t mgs_nearest_args_size(void);
+uint64_t mgs_nearest_scratch_bytes(int32_t num_ref);
+int32_t mgs_nearest_distance(const mgs_nearest_args* args, void* stream);
+int32_t mgs_mesh_eval_args_size(void);
+uint64_t mgs_mesh_eval_scratch_bytes(void);
+int32_t mgs_mesh_eval_stats(const mgs_mesh_eval_args* args, void* stream);
+int32_t mgs_mesh_eval_finish(const mgs_mesh_eval_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

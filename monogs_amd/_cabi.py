@@ -46,6 +46,9 @@ EXPORTS = (
     "mgs_tsdf_mesh_count", "mgs_tsdf_mesh_emit",
     "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
     "mgs_mesh_components",
+    "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
+    "mgs_nearest_args_size", "mgs_nearest_scratch_bytes", "mgs_nearest_distance",
+    "mgs_mesh_eval_args_size", "mgs_mesh_eval_scratch_bytes", "mgs_mesh_eval_stats", "mgs_mesh_eval_finish",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -397,6 +400,28 @@ class MeshCleanArgs(C.Structure):
                 + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
 
 
+MESH_EVAL_MAX_ITEMS = (2 ** 31 - 1) // 3      # 3 n < 2^31 for vertices, faces, samples, queries and reference points
+SAMPLE_RECORD_INTS = 4                        # MGS_SAMPLE_RECORD_INTS: T == 0, bad faces, low and high word of T
+NEAREST_MAX_CELLS, NEAREST_MAX_DIM = 1 << 21, 1024
+MESH_EVAL_RECORD_DOUBLES = 12                 # {n finite, n below, max d, sum d} x 2, then {T == 0, bad faces} x 2
+
+
+class SurfaceSampleArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "num_samples", "reserved0")]
+                + [("seed", C.c_uint64)]
+                + [(n, _fp) for n in ("verts", "faces", "randoms", "scratch", "points", "face_index", "record")])
+
+
+class NearestArgs(C.Structure):
+    _fields_ = ([("num_query", C.c_int32), ("num_ref", C.c_int32), ("cell_size", C.c_float), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("query", "ref", "scratch", "d2", "index")])
+
+
+class MeshEvalArgs(C.Structure):
+    _fields_ = ([("num", C.c_int32), ("direction", C.c_int32), ("threshold", C.c_float), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("d2", "scratch", "record")] + [("sample_record", _fp * 2)])
+
+
 _lib = None
 
 
@@ -601,6 +626,18 @@ def lib():
     L.mgs_mesh_clean_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     for fn in (L.mgs_mesh_clean_count, L.mgs_mesh_clean_emit, L.mgs_mesh_components):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshCleanArgs), C.c_void_p]
+    for size_fn, cls in ((L.mgs_surface_sample_args_size, SurfaceSampleArgs), (L.mgs_nearest_args_size, NearestArgs),
+                         (L.mgs_mesh_eval_args_size, MeshEvalArgs)):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    for fn in (L.mgs_surface_sample_scratch_bytes, L.mgs_nearest_scratch_bytes):
+        fn.restype, fn.argtypes = C.c_uint64, [C.c_int32]
+    L.mgs_mesh_eval_scratch_bytes.restype, L.mgs_mesh_eval_scratch_bytes.argtypes = C.c_uint64, []
+    L.mgs_surface_sample.restype, L.mgs_surface_sample.argtypes = C.c_int32, [C.POINTER(SurfaceSampleArgs), C.c_void_p]
+    L.mgs_nearest_distance.restype, L.mgs_nearest_distance.argtypes = C.c_int32, [C.POINTER(NearestArgs), C.c_void_p]
+    for fn in (L.mgs_mesh_eval_stats, L.mgs_mesh_eval_finish):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshEvalArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

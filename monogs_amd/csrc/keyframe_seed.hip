@@ -26,6 +26,7 @@
 
 #include "../../include/monogs_raster.h"
 #include "launch.h"
+#include "philox.h"
 #include "radix_select.h"
 #include "raster_kernels.h"
 #include "rn_math.h"
@@ -84,19 +85,7 @@ SeedLayout seed_layout(int num_pixels, int row_capacity) {
   return L;
 }
 
-// ---- Philox-4x32-10 (Salmon et al., SC'11), counter (pixel, 0, stream, 0), key = the two halves of the seed ---------
-__device__ __forceinline__ uint4 philox4x32_10(uint4 c, uint2 k) {
-#pragma unroll
-  for (int r = 0; r < 10; r++) {
-    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
-    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
-    c = make_uint4(hi1 ^ c.y ^ k.x, lo1, hi0 ^ c.w ^ k.y, lo0);
-    k.x += 0x9E3779B9u;
-    k.y += 0xBB67AE85u;
-  }
-  return c;
-}
-
+// ---- Philox-4x32-10 (philox.h), counter (pixel, 0, stream, 0), key = the two halves of the seed -------------------------
 __device__ __forceinline__ float draw_normal(uint64_t seed, unsigned pixel) {
   const uint4 r = philox4x32_10(make_uint4(pixel, 0u, 0u, 0u), make_uint2((unsigned)seed, (unsigned)(seed >> 32)));
   // 24-bit uniforms strictly inside (0, 1): exact in fp32

@@ -500,3 +500,22 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
     if clean is None:
         return vol.extract_mesh(min_weight)
     return vol.extract_mesh(min_weight, clean=clean)
+
+
+def evaluate_mesh(result, gt, voxel_size: float, monocular: bool = True, mesh_kw=None, **kw):
+    """The geometry scores of a finished run (mesh_eval.evaluate_mesh: accuracy, completion, precision / recall / F-score,
+    Chamfer) against `gt` - a (verts, faces) mesh or a point tensor [M,3] on the device, in the ground truth's frame.  The
+    surface is reconstruct_mesh(result, voxel_size, **mesh_kw); it is brought into the ground truth's frame by the
+    alignment `evaluate` uses for the ATE over all tracked frames - Sim(3) when `monocular`, SE(3) otherwise - and scored
+    with `kw` (n_samples, threshold, seed)."""
+    import numpy as np
+    from . import eval_metrics as E
+    from .mesh_eval import evaluate_mesh as score
+    cams = result["cameras"]
+    ids = sorted(cams)
+    centre = lambda T: np.linalg.inv(torch.as_tensor(T).double().cpu().numpy())[:3, 3]
+    est = np.stack([centre(cams[i].T) for i in ids], 1)
+    ref = np.stack([centre(cams[i].T_gt) for i in ids], 1)
+    R, t, c = E.umeyama_alignment(est, ref, with_scale=monocular)
+    verts, faces, _ = reconstruct_mesh(result, voxel_size, **(mesh_kw or {}))
+    return score((verts, faces), gt, transform=(c, R, t), **kw)
