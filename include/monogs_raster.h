@@ -1675,6 +1675,99 @@ uint64_t mgs_mesh_eval_scratch_bytes(void);
 int32_t mgs_mesh_eval_stats(const mgs_mesh_eval_args* args, void* stream);
 int32_t mgs_mesh_eval_finish(const mgs_mesh_eval_args* args, void* stream);
 
+/* ---- mesh rendering and culling ("Mesh rendering and culling") -----------------------------------------
+ * The depth image of a triangle mesh at a pose, the per-view visibility of vertices against such an image, and the cull
+ * of what too few views saw - what reconstruction benchmarks apply to both meshes before mgs_surface_sample.  Every
+ * output is an integer or a single IEEE rounding and independent of the execution order; the mirrors in
+ * monogs_amd/mesh_render.py are the contract and the device equals them bit for bit.
+ *
+ * Projection (render and visibility; tsdf's): with T [4,4] row-major world-to-camera on the device,
+ *   row(r) = ((T[r,0] x + T[r,1] y) + T[r,2] z) + T[r,3];  u = fx (xc / zc) + cx, v = fy (yc / zc) + cy; every operation
+ *   one fp32 rounding; pixel (x, y) is centred at u = x, v = y.
+ *
+ * mgs_mesh_render   depth [H,W] f32 (0 without a surface) and face_id [H,W] i32 (-1 without one) of (verts, faces).
+ *   snap      X = rint(256 u), Y = rint(256 v) as int32, round-half-even.
+ *   bad       a face with an index outside [0,V): counted in record[0], never drawn.
+ *   skipped   a face with a vertex that has !(zc > z_near), a non-finite zc, or !(|X| <= 2^24) or !(|Y| <= 2^24) (which
+ *             takes NaN and infinite u, v): counted in record[1].  There is NO near-plane clipping.
+ *   coverage  int64 edge functions of the snapped vertices at (256 x, 256 y), all three multiplied by the sign of the
+ *             doubled area 2A (2A = 0: the face is ignored); covered iff w0, w1, w2 >= 0 - inclusive, two-sided, no
+ *             top-left rule.  Only the pixels of the face's box clamped to the image are tested.
+ *   depth     iz_i = 1.0 / (double)zc_i; z = (float)((double)|2A| / ((w0 iz0 + w1 iz1) + w2 iz2)), every operation one
+ *             fp64 rounding, w_i the weight of vertex i in the face's own order.
+ *   winner    the minimum over the covering faces of the key (bits(z) << 32) | face: nearest, then smallest index.
+ *   paths     a face whose clamped box holds more than `large_threshold` pixels is appended to a device list and drawn by
+ *             a second launch of `large_grid` workgroups that stride the list, 256 threads striding the box; the others
+ *             are drawn by one lane each.  Both write the same keys.  record[2] = faces on the list, record[3] = 0.
+ *   Four launches (fill, faces, large faces, resolve), no host read.  `scratch`: mgs_mesh_render_scratch_bytes, no
+ *   initial state.
+ *
+ * mgs_vertex_visibility   seen_count[v] += 1 for every vertex with zc > z_near, (floor(u + 0.5), floor(v + 0.5)) inside
+ *   the image and - with `depth` [H,W] - d = depth[pixel]: !(d > 0) ? empty_visible : !((zc - d) > eps), one rounding
+ *   each.  One thread per vertex, one launch, no atomics.
+ *
+ * mgs_mesh_cull_count / mgs_mesh_cull_emit   keep a face iff its indices lie in [0,V) and all (rule 0) or any (rule 1)
+ *   of its vertices have seen_count >= min_views; keep the vertices a kept face names; both in their order, the faces
+ *   re-indexed.  count: counts = (V', F', bad faces, 0) on the device.  emit, after the caller has read counts: as
+ *   mgs_mesh_clean_emit.  `faces` and `seen_count` must not change in between.
+ *
+ * A null struct, scratch or needed array, a negative size, H or W < 1, a rule outside {0, 1}: MGS_ERR_BAD_ARGUMENT.
+ * 3 V, 3 F >= 2^31 or H W >= 2^31: MGS_ERR_UNSUPPORTED, and scratch_bytes is 0.  V = 0 or F = 0 is legal.  A refused call
+ * launches nothing and writes nothing. */
+#define MGS_MESH_RENDER_RECORD_INTS 4
+#define MGS_MESH_RENDER_LARGE_BOX 1024     /* the default large_threshold */
+#define MGS_MESH_RENDER_LARGE_GRID 256     /* the default large_grid */
+#define MGS_MESH_CULL_COUNTS 4
+
+typedef struct mgs_mesh_render_args {
+  int32_t num_verts, num_faces, width, height;
+  int32_t large_threshold;   /* >= 0; negative: MGS_MESH_RENDER_LARGE_BOX */
+  int32_t large_grid;        /* >= 1; 0: MGS_MESH_RENDER_LARGE_GRID */
+  float fx, fy, cx, cy, z_near;
+  int32_t reserved0;
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3] */
+  const float* T;            /* [4,4] device */
+  void* scratch;             /* mgs_mesh_render_scratch_bytes(height, width, num_faces) */
+  float* depth;              /* [H,W] out */
+  int32_t* face_id;          /* [H,W] out */
+  int32_t* record;           /* [MGS_MESH_RENDER_RECORD_INTS] device out */
+} mgs_mesh_render_args;
+
+typedef struct mgs_vertex_visibility_args {
+  int32_t num_verts, width, height, empty_visible;
+  float fx, fy, cx, cy, z_near, eps;
+  const float* verts;        /* [V,3] */
+  const float* T;            /* [4,4] device */
+  const float* depth;        /* [H,W] or NULL: the frustum alone */
+  int32_t* seen_count;       /* [V] incremented in place */
+} mgs_vertex_visibility_args;
+
+typedef struct mgs_mesh_cull_args {
+  int32_t num_verts, num_faces, min_views;
+  int32_t rule;              /* 0: all three vertices seen, 1: any */
+  const float* verts;        /* [V,3] (emit only) */
+  const int32_t* faces;      /* [F,3] */
+  const float* colors;       /* [V,3] or NULL (emit only) */
+  const int32_t* seen_count; /* [V] (count only) */
+  void* scratch;             /* mgs_mesh_cull_scratch_bytes(num_verts, num_faces) */
+  int32_t* counts;           /* [MGS_MESH_CULL_COUNTS] device (count only) */
+  float* out_verts;          /* [out_num_verts,3] (emit only) */
+  int32_t* out_faces;        /* [out_num_faces,3] (emit only) */
+  float* out_colors;         /* [out_num_verts,3] (emit only, with `colors`) */
+  int32_t out_num_verts, out_num_faces;   /* as read from counts[0], counts[1] (emit only) */
+} mgs_mesh_cull_args;
+
+int32_t mgs_mesh_render_args_size(void);
+uint64_t mgs_mesh_render_scratch_bytes(int32_t height, int32_t width, int32_t num_faces);
+int32_t mgs_mesh_render(const mgs_mesh_render_args* args, void* stream);
+int32_t mgs_vertex_visibility_args_size(void);
+int32_t mgs_vertex_visibility(const mgs_vertex_visibility_args* args, void* stream);
+int32_t mgs_mesh_cull_args_size(void);
+uint64_t mgs_mesh_cull_scratch_bytes(int32_t num_verts, int32_t num_faces);
+int32_t mgs_mesh_cull_count(const mgs_mesh_cull_args* args, void* stream);
+int32_t mgs_mesh_cull_emit(const mgs_mesh_cull_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

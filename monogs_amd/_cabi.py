@@ -49,6 +49,9 @@ EXPORTS = (
     "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
     "mgs_nearest_args_size", "mgs_nearest_scratch_bytes", "mgs_nearest_distance",
     "mgs_mesh_eval_args_size", "mgs_mesh_eval_scratch_bytes", "mgs_mesh_eval_stats", "mgs_mesh_eval_finish",
+    "mgs_mesh_render_args_size", "mgs_mesh_render_scratch_bytes", "mgs_mesh_render",
+    "mgs_vertex_visibility_args_size", "mgs_vertex_visibility",
+    "mgs_mesh_cull_args_size", "mgs_mesh_cull_scratch_bytes", "mgs_mesh_cull_count", "mgs_mesh_cull_emit",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -422,6 +425,32 @@ class MeshEvalArgs(C.Structure):
                 + [(n, _fp) for n in ("d2", "scratch", "record")] + [("sample_record", _fp * 2)])
 
 
+MESH_RENDER_RECORD_INTS = 4                   # MGS_MESH_RENDER_RECORD_INTS: bad faces, skipped faces, large faces, spare
+MESH_RENDER_LARGE_BOX = 1024                  # MGS_MESH_RENDER_LARGE_BOX: box pixels above which a face takes the large path
+MESH_RENDER_LARGE_GRID = 256                  # MGS_MESH_RENDER_LARGE_GRID: workgroups that stride the large-face list
+MESH_RENDER_MAX_PIXELS = 2 ** 31 - 1
+MESH_CULL_COUNTS = 4                          # V', F', bad faces, spare
+
+
+class MeshRenderArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "width", "height", "large_threshold", "large_grid")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "z_near")] + [("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("verts", "faces", "T", "scratch", "depth", "face_id", "record")])
+
+
+class VertexVisibilityArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "width", "height", "empty_visible")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "z_near", "eps")]
+                + [(n, _fp) for n in ("verts", "T", "depth", "seen_count")])
+
+
+class MeshCullArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "min_views", "rule")]
+                + [(n, _fp) for n in ("verts", "faces", "colors", "seen_count", "scratch", "counts", "out_verts",
+                                      "out_faces", "out_colors")]
+                + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
+
+
 _lib = None
 
 
@@ -638,6 +667,20 @@ def lib():
     L.mgs_nearest_distance.restype, L.mgs_nearest_distance.argtypes = C.c_int32, [C.POINTER(NearestArgs), C.c_void_p]
     for fn in (L.mgs_mesh_eval_stats, L.mgs_mesh_eval_finish):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshEvalArgs), C.c_void_p]
+    for size_fn, cls in ((L.mgs_mesh_render_args_size, MeshRenderArgs),
+                         (L.mgs_vertex_visibility_args_size, VertexVisibilityArgs),
+                         (L.mgs_mesh_cull_args_size, MeshCullArgs)):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    L.mgs_mesh_render_scratch_bytes.restype = C.c_uint64
+    L.mgs_mesh_render_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    L.mgs_mesh_cull_scratch_bytes.restype, L.mgs_mesh_cull_scratch_bytes.argtypes = C.c_uint64, [C.c_int32, C.c_int32]
+    L.mgs_mesh_render.restype, L.mgs_mesh_render.argtypes = C.c_int32, [C.POINTER(MeshRenderArgs), C.c_void_p]
+    L.mgs_vertex_visibility.restype = C.c_int32
+    L.mgs_vertex_visibility.argtypes = [C.POINTER(VertexVisibilityArgs), C.c_void_p]
+    for fn in (L.mgs_mesh_cull_count, L.mgs_mesh_cull_emit):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshCullArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

@@ -11,10 +11,10 @@
 //   k_cc_hist<1,2,3> (keep_largest given) the three histogram levels of radix_select.h over the face counts of the roots
 //   k_cc_threshold   one workgroup: the keep_largest-th largest count T, and how many clusters AT T still fit
 //   k_tie_prefix     (keep_largest given) rank of every root at T among the roots at T, in ascending label: in-block
-//   k_clean_scan     ... and the block bases (the same one-workgroup scan as below)
+//   k_compact_scan   ... and the block bases (the same one-workgroup scan as below)
 //   k_clean_flags    keep flag per vertex (through its label) and per face (through the label of its first index), the
 //                    in-block ranks of the kept ones, the block totals, the clusters and the kept clusters of the block
-//   k_clean_scan     ONE workgroup, 1024 block totals per trip: exclusive bases, grand totals to `counts`
+//   k_compact_scan   ONE workgroup, 1024 block totals per trip: exclusive bases, grand totals to `counts`
 //   k_clean_emit     gathers vertices and colours, writes the re-indexed faces; every store bounded by the host's counts
 //
 // Visibility.  During k_cc_hook workgroups on other XCDs write `parent`.  EVERY access to `parent` in that launch is an
@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/monogs_raster.h"
+#include "compact_scan.h"
 #include "launch.h"
 #include "radix_select.h"
 
@@ -36,7 +37,7 @@ namespace mgs {
 namespace mclean {
 
 constexpr int kThreads = 256;
-constexpr int kScanPer = 4;                               // block totals per thread and trip of k_clean_scan
+static_assert(kThreads == kCompactThreads, "block_scan2 scans a workgroup of kCompactThreads");
 constexpr long long kMaxItems = ((1ll << 31) - 1) / 3;    // 3 n < 2^31: 32-bit element indices of [n,3] arrays
 
 enum { kSelKeepAll = 0, kSelThreshold = 1, kSelNone = 2 };
@@ -223,30 +224,7 @@ __global__ __launch_bounds__(kThreads) void k_cc_threshold(Scratch S, int K) {
   }
 }
 
-// ---- scans ------------------------------------------------------------------------------------------------------------
-// exclusive scan of (v, f) over the workgroup's 256 threads; returns the totals in tv / tf
-__device__ __forceinline__ void block_scan2(unsigned& v, unsigned& f, unsigned& tv, unsigned& tf, unsigned (*s_w)[2]) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  unsigned iv = v, jf = f;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned a = __shfl_up(iv, off), b = __shfl_up(jf, off);
-    if (lane >= off) { iv += a; jf += b; }
-  }
-  __syncthreads();              // a previous trip's readers of s_w are done
-  if (lane == 63) { s_w[wave][0] = iv; s_w[wave][1] = jf; }
-  __syncthreads();
-  unsigned bv = 0, bf = 0;
-  tv = 0; tf = 0;
-#pragma unroll
-  for (int q = 0; q < kThreads / 64; q++) {
-    if (q < wave) { bv += s_w[q][0]; bf += s_w[q][1]; }
-    tv += s_w[q][0]; tf += s_w[q][1];
-  }
-  v = bv + iv - v;
-  f = bf + jf - f;
-}
-
+// ---- scans (block_scan2 and k_compact_scan: compact_scan.h) ---------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_tie_prefix(Scratch S, int V) {
   __shared__ unsigned s_w[kThreads / 64][2];
   const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -289,38 +267,6 @@ __global__ __launch_bounds__(kThreads) void k_clean_flags(const int* __restrict_
   if (i < V) S.vrel[i] = kv ? (int)v : -1;
   if (i < F) S.frel[i] = kf ? (int)f : -1;
   if (threadIdx.x == 0) S.base[blockIdx.x] = make_uint4(tv, tf, clusters, kept);
-}
-
-// One workgroup, kScanPer consecutive totals per thread, i.e. 1024 per trip: x and y become exclusive bases, z and w are
-// summed.  3 V, 3 F < 2^31 bound every total.  counts (may be null): V', F', clusters, kept clusters.
-__global__ __launch_bounds__(kThreads) void k_clean_scan(uint4* __restrict__ base, int nblocks, int* __restrict__ counts) {
-  __shared__ unsigned s_w[kThreads / 64][2];
-  unsigned cv = 0, cf = 0, cz = 0, cw = 0;
-  for (int b0 = 0; b0 < nblocks; b0 += kThreads * kScanPer) {
-    const int b = b0 + kScanPer * threadIdx.x;
-    uint4 t[kScanPer];
-    unsigned v = 0, f = 0, tv, tf;
-#pragma unroll
-    for (int q = 0; q < kScanPer; q++) {
-      t[q] = b + q < nblocks ? base[b + q] : make_uint4(0u, 0u, 0u, 0u);
-      v += t[q].x; f += t[q].y;
-      cz += t[q].z; cw += t[q].w;
-    }
-    block_scan2(v, f, tv, tf, s_w);
-    unsigned rv = cv + v, rf = cf + f;
-#pragma unroll
-    for (int q = 0; q < kScanPer; q++) {
-      if (b + q < nblocks) { base[b + q].x = rv; base[b + q].y = rf; }
-      rv += t[q].x; rf += t[q].y;
-    }
-    cv += tv; cf += tf;
-  }
-  if (!counts) return;
-  unsigned tz, tw;
-  block_scan2(cz, cw, tz, tw, s_w);      // used as the block's sum of z and w
-  if (threadIdx.x == 0) {
-    counts[0] = (int)cv; counts[1] = (int)cf; counts[2] = (int)tz; counts[3] = (int)tw;
-  }
 }
 
 __global__ __launch_bounds__(kThreads) void k_clean_emit(mgs_mesh_clean_args A, Scratch S) {
@@ -416,10 +362,10 @@ int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* a, void* stream) {
     launch("cc_hist3", mclean::k_cc_hist<3>, dim3(vblocks), th, st, S, V, K);
     launch("cc_threshold", mclean::k_cc_threshold, dim3(1), th, st, S, K);
     launch("tie_prefix", mclean::k_tie_prefix, dim3(vblocks), th, st, S, V);
-    launch("tie_scan", mclean::k_clean_scan, dim3(1), th, st, S.tbase, vblocks, (int*)nullptr);
+    launch("tie_scan", k_compact_scan, dim3(1), th, st, S.tbase, vblocks, (int*)nullptr);
   }
   if (blocks > 0) launch("clean_flags", mclean::k_clean_flags, dim3(blocks), th, st, a->faces, V, F, V > 0 ? K : -1, a->min_faces, S);
-  launch("clean_scan", mclean::k_clean_scan, dim3(1), th, st, S.base, blocks, a->counts);
+  launch("clean_scan", k_compact_scan, dim3(1), th, st, S.base, blocks, a->counts);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 

@@ -19,4 +19,18 @@ __device__ __forceinline__ float sub_rn(float a, float b) {
   return a - b;
 }
 
+// fp64 (mesh_render.hip): the same, against a NumPy float64 mirror
+__device__ __forceinline__ double mul_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ double add_rn(double a, double b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ double div_rn(double a, double b) {      // IEEE division: correctly rounded
+#pragma clang fp contract(off)
+  return a / b;
+}
+
 }  // namespace mgs

@@ -282,7 +282,7 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
-              **fuse_kw):
+              cull=None, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -290,7 +290,8 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     keyword arguments, e.g. dict(keep_largest=1) - drops the floaters before the file is written.  Returns the path, or
     None without a name.  With `gt` - a (verts, faces) mesh or a point tensor [M,3] on the device - the mesh is scored
     against it (mesh_eval.evaluate_mesh, which takes `eval_kw`), the scores are written as mesh_eval.json next to
-    mesh.ply, and the dict of scores is returned instead of the path."""
+    mesh.ply, and the dict of scores is returned instead of the path.  `cull` - evaluate_mesh's dict(views=..., ...) - culls
+    both meshes by visibility first; the scores then hold culled_pred_faces and culled_gt_faces."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -310,6 +311,8 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         return path
     import json
     from .mesh_eval import evaluate_mesh
+    if cull is not None:
+        eval_kw = dict(eval_kw or {}, cull=cull)
     scores = evaluate_mesh((verts, faces), gt, **(eval_kw or {}))
     with open(os.path.join(name, sub, "mesh_eval.json"), "w", encoding="utf-8") as fh:
         json.dump(scores, fh, indent=4)

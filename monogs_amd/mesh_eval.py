@@ -204,10 +204,30 @@ def _is_mesh(gt):
     return isinstance(gt, (tuple, list)) and len(gt) == 2
 
 
+def _cull_arguments(cull, gt):
+    """The keyword arguments of mesh_render.cull_pair from evaluate_mesh's `cull` dict."""
+    if not isinstance(cull, dict) or "views" not in cull:
+        raise ValueError("evaluate_mesh: cull must be a dict with the key 'views' (and occlusion, eps, min_views, rule)")
+    if not _is_mesh(gt):
+        raise ValueError("evaluate_mesh: cull needs the ground truth as a (verts, faces) mesh")
+    unknown = set(cull) - {"views", "occlusion", "eps", "min_views", "rule", "empty_visible", "z_near"}
+    if unknown:
+        raise ValueError(f"evaluate_mesh: unknown cull keys {sorted(unknown)}")
+    kw = dict(cull)
+    kw.setdefault("occlusion", "gt")
+    return kw
+
+
 def evaluate_mesh_numpy(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, seed: int = 0, transform=None,
-                        with_record: bool = False):
-    """The mirror of evaluate_mesh on the host: the NumPy sampler, the brute-force distances (CPU torch), fp64 sums."""
+                        with_record: bool = False, cull=None):
+    """The mirror of evaluate_mesh on the host: the NumPy sampler, the brute-force distances (CPU torch), fp64 sums;
+    `cull` through the mirrors of mesh_render."""
     pv = apply_transform(torch.as_tensor(np.asarray(pred[0], np.float32)).reshape(-1, 3), transform).numpy()
+    culled = None
+    if cull is not None:
+        from .mesh_render import cull_pair
+        pred, gt, *culled = cull_pair(True, (pv, pred[1]), gt, **_cull_arguments(cull, gt))
+        pv = pred[0]
     pp, _, prec = sample_surface_numpy(pv, pred[1], n_samples, seed, with_record=True)
     if _is_mesh(gt):
         gp, _, grec = sample_surface_numpy(gt[0], gt[1], n_samples, seed + 1, with_record=True)
@@ -219,6 +239,8 @@ def evaluate_mesh_numpy(pred, gt, n_samples: int = 200_000, threshold: float = 0
         record[4 * d:4 * d + 4] = st["n"], st["below"], st["max"], st["sum"]
     record[8:12] = prec[0], prec[1], grec[0], grec[1]
     out = metrics_from_record(record, pp.shape[0], gp.shape[0])
+    if culled is not None:
+        out["culled_pred_faces"], out["culled_gt_faces"] = culled
     return (out, record) if with_record else out
 
 
@@ -345,16 +367,29 @@ def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_record
 
 
 def evaluate_mesh(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, seed: int = 0, transform=None,
-                  with_record: bool = False):
+                  with_record: bool = False, cull=None):
     """The geometry scores of the mesh `pred` = (verts, faces) against `gt` = (verts, faces), or a point tensor [M,3]
     that is used as it is: a dict of METRIC_KEYS, in the units of the input.  `transform` - (s, R, t) or a 4x4 matrix,
     e.g. the Sim(3) of the trajectory alignment - is applied to pred's vertices first (apply_transform).  pred is
     sampled with `seed`, gt with `seed + 1`; ONE host read, of the record; bad faces or a mesh without area raise
-    ValueError after it."""
+    ValueError after it.
+
+    `cull` = dict(views=..., occlusion="gt" | "self" | None, eps=0.05, min_views=1, rule="all") applies the visibility
+    protocol of mesh_render first: after `transform`, in the ground truth's frame, both meshes lose what fewer than
+    `min_views` of `views` (the ground-truth poses) saw - "gt" tests both against the ground-truth mesh's rendered depth,
+    "self" each against its own, None the frustum alone - and what is left is scored.  The dict then also holds
+    culled_pred_faces and culled_gt_faces, and each of the two culls adds one host read (of its counts)."""
     what = "evaluate_mesh"
     pv = _device_points(pred[0], what, "pred verts").detach().to(torch.float32)
     dev = pv.device
-    pp, _, prec = sample_surface(apply_transform(pv, transform), pred[1], n_samples, seed, with_record=True)
+    pv = apply_transform(pv, transform)
+    culled = None
+    if cull is not None:
+        from .mesh_render import cull_pair
+        kw = _cull_arguments(cull, gt)
+        pred, gt, *culled = cull_pair(False, (pv, pred[1]), (_device_points(gt[0], what, "gt verts", dev), gt[1]), **kw)
+        pv = pred[0]
+    pp, _, prec = sample_surface(pv, pred[1], n_samples, seed, with_record=True)
     if _is_mesh(gt):
         gp, _, grec = sample_surface(_device_points(gt[0], what, "gt verts", dev), gt[1], n_samples, seed + 1,
                                      with_record=True)
@@ -364,4 +399,6 @@ def evaluate_mesh(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, s
     d_gp, _ = nearest_distance(gp, pp)
     record = distance_stats(d_pg, d_gp, threshold, (prec, grec)).cpu().numpy()        # the one host read
     out = metrics_from_record(record, pp.shape[0], gp.shape[0])
+    if culled is not None:
+        out["culled_pred_faces"], out["culled_gt_faces"] = culled
     return (out, record) if with_record else out

@@ -502,17 +502,25 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
     return vol.extract_mesh(min_weight, clean=clean)
 
 
-def evaluate_mesh(result, gt, voxel_size: float, monocular: bool = True, mesh_kw=None, **kw):
+def evaluate_mesh(result, gt, voxel_size: float, monocular: bool = True, mesh_kw=None, cull=None, **kw):
     """The geometry scores of a finished run (mesh_eval.evaluate_mesh: accuracy, completion, precision / recall / F-score,
     Chamfer) against `gt` - a (verts, faces) mesh or a point tensor [M,3] on the device, in the ground truth's frame.  The
     surface is reconstruct_mesh(result, voxel_size, **mesh_kw); it is brought into the ground truth's frame by the
     alignment `evaluate` uses for the ATE over all tracked frames - Sim(3) when `monocular`, SE(3) otherwise - and scored
-    with `kw` (n_samples, threshold, seed)."""
+    with `kw` (n_samples, threshold, seed).  `cull` - True, or a dict of mesh_eval.evaluate_mesh's cull keys (occlusion,
+    eps, min_views, rule) - applies the visibility protocol first, with the views built from the cameras' ground-truth
+    poses T_gt, their intrinsics and their image size (a dict may bring its own `views`)."""
     import numpy as np
     from . import eval_metrics as E
     from .mesh_eval import evaluate_mesh as score
     cams = result["cameras"]
     ids = sorted(cams)
+    if cull is not None and cull is not False:
+        cull = {} if cull is True else dict(cull)
+        if "views" not in cull:
+            cull["views"] = [(torch.as_tensor(cams[i].T_gt).float(), cams[i].fx, cams[i].fy, cams[i].cx, cams[i].cy,
+                              cams[i].image_height, cams[i].image_width) for i in ids]
+        kw["cull"] = cull
     centre = lambda T: np.linalg.inv(torch.as_tensor(T).double().cpu().numpy())[:3, 3]
     est = np.stack([centre(cams[i].T) for i in ids], 1)
     ref = np.stack([centre(cams[i].T_gt) for i in ids], 1)
