@@ -11,11 +11,12 @@
 //   k_cc_hist<1,2,3> (keep_largest given) the three histogram levels of radix_select.h over the face counts of the roots
 //   k_cc_threshold   one workgroup: the keep_largest-th largest count T, and how many clusters AT T still fit
 //   k_tie_prefix     (keep_largest given) rank of every root at T among the roots at T, in ascending label: in-block
-//   k_compact_scan   ... and the block bases (the same one-workgroup scan as below)
+//   k_compact_scan   ... and the block bases
 //   k_clean_flags    keep flag per vertex (through its label) and per face (through the label of its first index), the
 //                    in-block ranks of the kept ones, the block totals, the clusters and the kept clusters of the block
 //   k_compact_scan   ONE workgroup, 1024 block totals per trip: exclusive bases, grand totals to `counts`
-//   k_clean_emit     gathers vertices and colours, writes the re-indexed faces; every store bounded by the host's counts
+//   k_compact_emit   gathers vertices and colours, writes the re-indexed faces; every store bounded by the host's counts
+//                    (both: compact_scan.h)
 //
 // Visibility.  During k_cc_hook workgroups on other XCDs write `parent`.  EVERY access to `parent` in that launch is an
 // agent-scope relaxed atomic (load, compare-exchange, min): a plain load may return a stale line of this CU's L1 - that
@@ -38,7 +39,6 @@ namespace mclean {
 
 constexpr int kThreads = 256;
 static_assert(kThreads == kCompactThreads, "block_scan2 scans a workgroup of kCompactThreads");
-constexpr long long kMaxItems = ((1ll << 31) - 1) / 3;    // 3 n < 2^31: 32-bit element indices of [n,3] arrays
 
 enum { kSelKeepAll = 0, kSelThreshold = 1, kSelNone = 2 };
 
@@ -55,45 +55,21 @@ struct Scratch {
   int* sel;         // [4] mode, T, ties kept
 };
 
-__host__ __device__ inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline size_t blocks_of(size_t n) { return (n + kThreads - 1) / kThreads; }
-
-struct Layout {
-  size_t parent, label, count, trel, vrel, frel, tbase, base, hist, sel, bytes;
-};
-
-static Layout layout_of(size_t V, size_t F) {
-  Layout L;
-  size_t o = 0;
-  const size_t vplane = pad256(4 * V), fplane = pad256(4 * F);
-  L.hist = o; o += pad256(4 * (size_t)kRadixHistInts);
-  L.sel = o; o += 256;
-  L.parent = o; o += vplane;
-  L.label = o; o += vplane;
-  L.count = o; o += vplane;
-  L.trel = o; o += vplane;
-  L.vrel = o; o += vplane;
-  L.frel = o; o += fplane;
-  L.tbase = o; o += pad256(sizeof(uint4) * blocks_of(V));
-  L.base = o; o += pad256(sizeof(uint4) * blocks_of(V > F ? V : F));
-  L.bytes = o;
-  return L;
-}
-
-static Scratch scratch_of(void* p, size_t V, size_t F) {
-  const Layout L = layout_of(V, F);
-  char* c = static_cast<char*>(p);
-  Scratch S;
-  S.parent = reinterpret_cast<int*>(c + L.parent);
-  S.label = reinterpret_cast<int*>(c + L.label);
-  S.count = reinterpret_cast<int*>(c + L.count);
-  S.trel = reinterpret_cast<int*>(c + L.trel);
-  S.vrel = reinterpret_cast<int*>(c + L.vrel);
-  S.frel = reinterpret_cast<int*>(c + L.frel);
-  S.tbase = reinterpret_cast<uint4*>(c + L.tbase);
-  S.base = reinterpret_cast<uint4*>(c + L.base);
-  S.hist = radix_hists_at(c + L.hist);
-  S.sel = reinterpret_cast<int*>(c + L.sel);
+// the planes of the scratch buffer at p, in their order; *bytes (if given): their size (p may then be null)
+static Scratch scratch_of(void* p, size_t V, size_t F, size_t* bytes = nullptr) {
+  Carver c(p);
+  Scratch S{};
+  if (int* h = c.take<int>(kRadixHistInts)) S.hist = radix_hists_at(h);
+  S.sel = c.take<int>();
+  S.parent = c.take<int>(V);
+  S.label = c.take<int>(V);
+  S.count = c.take<int>(V);
+  S.trel = c.take<int>(V);
+  S.vrel = c.take<int>(V);
+  S.frel = c.take<int>(F);
+  S.tbase = c.take<uint4>((size_t)grid_of((long long)V));
+  S.base = c.take<uint4>((size_t)grid_of((long long)(V > F ? V : F)));
+  if (bytes) *bytes = c.bytes;
   return S;
 }
 
@@ -224,7 +200,7 @@ __global__ __launch_bounds__(kThreads) void k_cc_threshold(Scratch S, int K) {
   }
 }
 
-// ---- scans (block_scan2 and k_compact_scan: compact_scan.h) ---------------------------------------------------------
+// ---- scans (block_scan2: block_scan.h; k_compact_scan and the emit: compact_scan.h) -------------------------------------
 __global__ __launch_bounds__(kThreads) void k_tie_prefix(Scratch S, int V) {
   __shared__ unsigned s_w[kThreads / 64][2];
   const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -269,49 +245,6 @@ __global__ __launch_bounds__(kThreads) void k_clean_flags(const int* __restrict_
   if (threadIdx.x == 0) S.base[blockIdx.x] = make_uint4(tv, tf, clusters, kept);
 }
 
-__global__ __launch_bounds__(kThreads) void k_clean_emit(mgs_mesh_clean_args A, Scratch S) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  const int V = A.num_verts, F = A.num_faces;
-  if (i < V) {
-    const int r = S.vrel[i];
-    if (r >= 0) {
-      const unsigned id = S.base[i / kThreads].x + (unsigned)r;
-      if (id < (unsigned)A.out_num_verts) {
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) A.out_verts[3 * (size_t)id + ax] = A.verts[3 * (size_t)i + ax];
-        if (A.colors && A.out_colors) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ch++) A.out_colors[3 * (size_t)id + ch] = A.colors[3 * (size_t)i + ch];
-        }
-      }
-    }
-  }
-  if (i < F) {
-    const int r = S.frel[i];
-    if (r >= 0) {
-      const unsigned fid = S.base[i / kThreads].y + (unsigned)r;
-      if (fid < (unsigned)A.out_num_faces) {
-#pragma unroll
-        for (int e = 0; e < 3; e++) {
-          const int v = A.faces[3 * (size_t)i + e];
-          int id = -1;                                  // only if the faces changed since the count
-          if ((unsigned)v < (unsigned)V) id = (int)S.base[v / kThreads].x + S.vrel[v];
-          A.out_faces[3 * (size_t)fid + e] = id;
-        }
-      }
-    }
-  }
-}
-
-static int32_t size_status(const mgs_mesh_clean_args* a) {
-  if (!a || a->num_verts < 0 || a->num_faces < 0 || !a->scratch) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_faces > 0 && !a->faces) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_verts > kMaxItems || a->num_faces > kMaxItems) return MGS_ERR_UNSUPPORTED;
-  return MGS_OK;
-}
-
-static int grid_of(int n) { return (int)blocks_of((size_t)n); }
-
 // launches 1-3; `label` and `count` as k_cc_flatten takes them
 static void launch_components(const mgs_mesh_clean_args* a, const Scratch& S, int* label, int* count, hipStream_t st) {
   const int V = a->num_verts, F = a->num_faces;
@@ -333,12 +266,12 @@ extern "C" {
 int32_t mgs_mesh_clean_args_size(void) { return (int32_t)sizeof(mgs_mesh_clean_args); }
 
 uint64_t mgs_mesh_clean_scratch_bytes(int32_t num_verts, int32_t num_faces) {
-  if (num_verts < 0 || num_faces < 0 || num_verts > mclean::kMaxItems || num_faces > mclean::kMaxItems) return 0;
-  return mclean::layout_of((size_t)num_verts, (size_t)num_faces).bytes;
+  if (num_verts < 0 || num_faces < 0 || num_verts > kMaxItems || num_faces > kMaxItems) return 0;
+  return carved_bytes(mclean::scratch_of, (size_t)num_verts, (size_t)num_faces);
 }
 
 int32_t mgs_mesh_components(const mgs_mesh_clean_args* a, void* stream) {
-  const int32_t rc = mclean::size_status(a);
+  const int32_t rc = mesh_sizes_status(a);
   if (rc != MGS_OK) return rc;
   if (a->num_verts > 0 && !a->labels) return MGS_ERR_BAD_ARGUMENT;
   const mclean::Scratch S = mclean::scratch_of(a->scratch, (size_t)a->num_verts, (size_t)a->num_faces);
@@ -347,7 +280,7 @@ int32_t mgs_mesh_components(const mgs_mesh_clean_args* a, void* stream) {
 }
 
 int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* a, void* stream) {
-  const int32_t rc = mclean::size_status(a);
+  const int32_t rc = mesh_sizes_status(a);
   if (rc != MGS_OK) return rc;
   if (!a->counts || a->keep_largest < -1 || a->min_faces < 0) return MGS_ERR_BAD_ARGUMENT;
   const int V = a->num_verts, F = a->num_faces, K = a->keep_largest;
@@ -355,7 +288,7 @@ int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* a, void* stream) {
   hipStream_t st = (hipStream_t)stream;
   const dim3 th(mclean::kThreads);
   mclean::launch_components(a, S, S.label, S.count, st);
-  const int vblocks = mclean::grid_of(V), blocks = mclean::grid_of(V > F ? V : F);
+  const int vblocks = grid_of(V), blocks = grid_of(V > F ? V : F);
   if (K >= 0 && V > 0) {
     launch("cc_hist1", mclean::k_cc_hist<1>, dim3(vblocks), th, st, S, V, K);
     launch("cc_hist2", mclean::k_cc_hist<2>, dim3(vblocks), th, st, S, V, K);
@@ -370,17 +303,10 @@ int32_t mgs_mesh_clean_count(const mgs_mesh_clean_args* a, void* stream) {
 }
 
 int32_t mgs_mesh_clean_emit(const mgs_mesh_clean_args* a, void* stream) {
-  const int32_t rc = mclean::size_status(a);
+  const int32_t rc = mesh_sizes_status(a);
   if (rc != MGS_OK) return rc;
-  if (a->out_num_verts < 0 || a->out_num_faces < 0) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_verts > a->num_verts || a->out_num_faces > a->num_faces) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_verts == 0 && a->out_num_faces == 0) return MGS_OK;
-  if (a->out_num_verts > 0 && (!a->verts || !a->out_verts || (a->colors && !a->out_colors))) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_faces > 0 && !a->out_faces) return MGS_ERR_BAD_ARGUMENT;
-  const int V = a->num_verts, F = a->num_faces;
-  const mclean::Scratch S = mclean::scratch_of(a->scratch, (size_t)V, (size_t)F);
-  launch("clean_emit", mclean::k_clean_emit, dim3(mclean::grid_of(V > F ? V : F)), dim3(mclean::kThreads), (hipStream_t)stream, *a, S);
-  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+  const mclean::Scratch S = mclean::scratch_of(a->scratch, (size_t)a->num_verts, (size_t)a->num_faces);
+  return compact_emit("clean_emit", compact_emit_of(*a, S.vrel, S.frel, S.base), (hipStream_t)stream);
 }
 
 }  // extern "C"

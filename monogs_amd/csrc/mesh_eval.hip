@@ -7,7 +7,8 @@
 //   k_area_max       ONE workgroup: the maximum and the bad faces of all blocks into the header (no atomics)
 //   k_face_cdf       q = uint32(A * 2^(30 - E)) by an exact fp64 scaling, inclusive scan of q inside the block (uint64),
 //                    the block's total
-//   k_cdf_scan       ONE workgroup, 1024 block totals per trip with a carry: inclusive block sums, T, the record
+//   k_cdf_scan       ONE workgroup, 1024 block totals per trip with a carry (scan_block_totals, block_scan.h): inclusive
+//                    block sums, T, the record
 //   k_sample         one thread per sample: words, t = words mod T, block by binary search over the block sums, face by
 //                    binary search inside the block, folded barycentric pair, point
 // mgs_nearest_distance
@@ -17,7 +18,7 @@
 //   k_nn_clear       cell counts = 0
 //   k_nn_count       cell of every reference point (-1: not finite), integer histogram
 //   k_nn_cellscan    exclusive scan of the counts inside blocks of 256 cells, block totals
-//   k_nn_scan_totals ONE workgroup, 1024 totals per trip with a carry
+//   k_nn_scan_totals ONE workgroup: the same scan_block_totals, exclusive, the total behind the last block
 //   k_nn_cellstart   absolute start of every cell, and the end of the last
 //   k_nn_scatter     points into their cells (x, y, z, original index); the place inside a cell is whatever the atomic
 //                    gives - the query's (d2, index) rule makes the order invisible
@@ -41,46 +42,21 @@
 #include <math.h>
 
 #include "../../include/monogs_raster.h"
+#include "block_scan.h"
 #include "launch.h"
 #include "philox.h"
 #include "rn_math.h"
+#include "scratch_carve.h"
 
 namespace mgs {
 namespace meval {
 
 constexpr int kThreads = 256;
-constexpr int kScanPer = 4;                               // block totals per thread and trip of the one-workgroup scans
-constexpr long long kMaxItems = ((1ll << 31) - 1) / 3;    // 3 n < 2^31
+static_assert(kThreads == kCompactThreads, "block_scan_incl scans a workgroup of kCompactThreads");
 constexpr int kMaxCells = MGS_NEAREST_MAX_CELLS;
 constexpr int kMaxDim = MGS_NEAREST_MAX_DIM;
 constexpr int kCellBlocks = kMaxCells / kThreads;         // 8192
 constexpr int kStatBlocks = 256;
-
-__host__ __device__ inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline size_t blocks_of(size_t n) { return (n + kThreads - 1) / kThreads; }
-static int grid_of(int n) { return (int)blocks_of((size_t)n); }
-
-// inclusive scan of v over the workgroup's 256 threads; the total in `total`
-__device__ __forceinline__ unsigned long long block_scan_incl(unsigned long long v, unsigned long long& total,
-                                                              unsigned long long* s_w) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int off = 1; off < 64; off <<= 1) {
-    const unsigned long long a = __shfl_up(v, off);
-    if (lane >= off) v += a;
-  }
-  __syncthreads();              // a previous trip's readers of s_w are done
-  if (lane == 63) s_w[wave] = v;
-  __syncthreads();
-  unsigned long long base = 0;
-  total = 0;
-#pragma unroll
-  for (int q = 0; q < kThreads / 64; q++) {
-    if (q < wave) base += s_w[q];
-    total += s_w[q];
-  }
-  return base + v;
-}
 
 // ---- surface sampling --------------------------------------------------------------------------------------------------
 struct SampleHeader {
@@ -96,15 +72,15 @@ struct SampleScratch {
   unsigned long long* bsum;     // [blocks(F)] inclusive sums of the block totals
 };
 
-static size_t sample_bytes(size_t F) { return 256 + pad256(4 * F) + pad256(8 * F) + pad256(8 * blocks_of(F)); }
-
-static SampleScratch sample_scratch_of(void* p, size_t F) {
-  char* c = static_cast<char*>(p);
+// the planes of the scratch buffer at p, in their order; *bytes (if given): their size (p may then be null)
+static SampleScratch sample_scratch_of(void* p, size_t F, size_t* bytes = nullptr) {
+  Carver c(p);
   SampleScratch S;
-  S.hdr = reinterpret_cast<SampleHeader*>(c);
-  S.area = reinterpret_cast<unsigned*>(c + 256);
-  S.local = reinterpret_cast<unsigned long long*>(c + 256 + pad256(4 * F));
-  S.bsum = reinterpret_cast<unsigned long long*>(c + 256 + pad256(4 * F) + pad256(8 * F));
+  S.hdr = c.take<SampleHeader>();
+  S.area = c.take<unsigned>(F);
+  S.local = c.take<unsigned long long>(F);
+  S.bsum = c.take<unsigned long long>((size_t)grid_of((long long)F));
+  if (bytes) *bytes = c.bytes;
   return S;
 }
 
@@ -195,26 +171,12 @@ __global__ __launch_bounds__(kThreads) void k_face_cdf(int F, SampleScratch S) {
   if (threadIdx.x == 0) S.bsum[blockIdx.x] = total;
 }
 
-// One workgroup, kScanPer consecutive totals per thread, i.e. 1024 per trip: the totals become inclusive sums.
+// The one-workgroup scan of the block totals (scan_block_totals): they become inclusive sums.
 __global__ __launch_bounds__(kThreads) void k_cdf_scan(SampleScratch S, int nblocks, int* __restrict__ record) {
   __shared__ unsigned long long s_w[kThreads / 64];
-  unsigned long long carry = 0;
-  for (int b0 = 0; b0 < nblocks; b0 += kThreads * kScanPer) {
-    const int b = b0 + kScanPer * threadIdx.x;
-    unsigned long long t[kScanPer], v = 0, total;
-#pragma unroll
-    for (int k = 0; k < kScanPer; k++) {
-      t[k] = b + k < nblocks ? S.bsum[b + k] : 0ull;
-      v += t[k];
-    }
-    unsigned long long run = carry + block_scan_incl(v, total, s_w) - v;
-#pragma unroll
-    for (int k = 0; k < kScanPer; k++) {
-      run += t[k];
-      if (b + k < nblocks) S.bsum[b + k] = run;
-    }
-    carry += total;
-  }
+  const unsigned long long carry = scan_block_totals(
+      nblocks, s_w, [&](int b) { return S.bsum[b]; },
+      [&](int b, unsigned long long run, unsigned long long own) { S.bsum[b] = run + own; });
   if (threadIdx.x == 0) {
     S.hdr->total = carry;
     record[0] = carry == 0 ? 1 : 0;
@@ -292,30 +254,17 @@ struct GridScratch {
   float4* pts;       // [Q] (x, y, z, bits of the original index), by cell
 };
 
-struct GridLayout { size_t count, cstart, btot, cell, pts, bytes; };
-
-static GridLayout grid_layout(size_t Q) {
-  GridLayout L;
-  size_t o = 256;
-  L.count = o; o += pad256(4 * (size_t)kMaxCells);
-  L.cstart = o; o += pad256(4 * ((size_t)kMaxCells + 1));
-  L.btot = o; o += pad256(4 * ((size_t)kCellBlocks + 1));
-  L.cell = o; o += pad256(4 * Q);
-  L.pts = o; o += pad256(16 * Q);
-  L.bytes = o;
-  return L;
-}
-
-static GridScratch grid_scratch_of(void* p, size_t Q) {
-  const GridLayout L = grid_layout(Q);
-  char* c = static_cast<char*>(p);
+// the planes of the scratch buffer at p, in their order; *bytes (if given): their size (p may then be null)
+static GridScratch grid_scratch_of(void* p, size_t Q, size_t* bytes = nullptr) {
+  Carver c(p);
   GridScratch S;
-  S.hdr = reinterpret_cast<GridHeader*>(c);
-  S.count = reinterpret_cast<int*>(c + L.count);
-  S.cstart = reinterpret_cast<int*>(c + L.cstart);
-  S.btot = reinterpret_cast<int*>(c + L.btot);
-  S.cell = reinterpret_cast<int*>(c + L.cell);
-  S.pts = reinterpret_cast<float4*>(c + L.pts);
+  S.hdr = c.take<GridHeader>();
+  S.count = c.take<int>((size_t)kMaxCells);
+  S.cstart = c.take<int>((size_t)kMaxCells + 1);
+  S.btot = c.take<int>((size_t)kCellBlocks + 1);
+  S.cell = c.take<int>(Q);
+  S.pts = c.take<float4>(Q);
+  if (bytes) *bytes = c.bytes;
   return S;
 }
 
@@ -469,23 +418,9 @@ __global__ __launch_bounds__(kThreads) void k_nn_cellscan(GridScratch S) {
 __global__ __launch_bounds__(kThreads) void k_nn_scan_totals(GridScratch S) {
   __shared__ unsigned long long s_w[kThreads / 64];
   const int nblocks = min(S.hdr->nblocks, kCellBlocks);
-  unsigned long long carry = 0;
-  for (int b0 = 0; b0 < nblocks; b0 += kThreads * kScanPer) {
-    const int b = b0 + kScanPer * threadIdx.x;
-    unsigned long long t[kScanPer], v = 0, total;
-#pragma unroll
-    for (int k = 0; k < kScanPer; k++) {
-      t[k] = b + k < nblocks ? (unsigned long long)S.btot[b + k] : 0ull;
-      v += t[k];
-    }
-    unsigned long long run = carry + block_scan_incl(v, total, s_w) - v;
-#pragma unroll
-    for (int k = 0; k < kScanPer; k++) {
-      if (b + k < nblocks) S.btot[b + k] = (int)run;
-      run += t[k];
-    }
-    carry += total;
-  }
+  const unsigned long long carry = scan_block_totals(
+      nblocks, s_w, [&](int b) { return (unsigned long long)S.btot[b]; },
+      [&](int b, unsigned long long run, unsigned long long) { S.btot[b] = (int)run; });
   if (threadIdx.x == 0) S.btot[nblocks] = (int)carry;
 }
 
@@ -643,13 +578,13 @@ int32_t mgs_nearest_args_size(void) { return (int32_t)sizeof(mgs_nearest_args); 
 int32_t mgs_mesh_eval_args_size(void) { return (int32_t)sizeof(mgs_mesh_eval_args); }
 
 uint64_t mgs_surface_sample_scratch_bytes(int32_t num_faces) {
-  if (num_faces < 0 || num_faces > meval::kMaxItems) return 0;
-  return meval::sample_bytes((size_t)num_faces);
+  if (num_faces < 0 || num_faces > kMaxItems) return 0;
+  return carved_bytes(meval::sample_scratch_of, (size_t)num_faces);
 }
 
 uint64_t mgs_nearest_scratch_bytes(int32_t num_ref) {
-  if (num_ref < 0 || num_ref > meval::kMaxItems) return 0;
-  return meval::grid_layout((size_t)num_ref).bytes;
+  if (num_ref < 0 || num_ref > kMaxItems) return 0;
+  return carved_bytes(meval::grid_scratch_of, (size_t)num_ref);
 }
 
 uint64_t mgs_mesh_eval_scratch_bytes(void) { return 2 * (uint64_t)meval::kStatBlocks * sizeof(meval::StatPartial); }
@@ -659,18 +594,18 @@ int32_t mgs_surface_sample(const mgs_surface_sample_args* a, void* stream) {
     return MGS_ERR_BAD_ARGUMENT;
   if (a->num_faces > 0 && (!a->faces || (a->num_verts > 0 && !a->verts))) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_samples > 0 && (!a->points || !a->face_index)) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_verts > meval::kMaxItems || a->num_faces > meval::kMaxItems || a->num_samples > meval::kMaxItems)
+  if (a->num_verts > kMaxItems || a->num_faces > kMaxItems || a->num_samples > kMaxItems)
     return MGS_ERR_UNSUPPORTED;
   const int V = a->num_verts, F = a->num_faces, n = a->num_samples;
   const meval::SampleScratch S = meval::sample_scratch_of(a->scratch, (size_t)F);
   hipStream_t st = (hipStream_t)stream;
   const dim3 th(meval::kThreads);
-  const int blocks = meval::grid_of(F);
+  const int blocks = grid_of(F);
   if (F > 0) launch("face_area", meval::k_face_area, dim3(blocks), th, st, a->verts, a->faces, V, F, S);
   launch("area_max", meval::k_area_max, dim3(1), th, st, S, blocks);
   if (F > 0) launch("face_cdf", meval::k_face_cdf, dim3(blocks), th, st, F, S);
   launch("cdf_scan", meval::k_cdf_scan, dim3(1), th, st, S, blocks, a->record);
-  if (n > 0) launch("sample", meval::k_sample, dim3(meval::grid_of(n)), th, st, *a, S);
+  if (n > 0) launch("sample", meval::k_sample, dim3(grid_of(n)), th, st, *a, S);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
@@ -678,28 +613,28 @@ int32_t mgs_nearest_distance(const mgs_nearest_args* a, void* stream) {
   if (!a || a->num_query < 0 || a->num_ref < 0 || !a->scratch || !(a->cell_size >= 0.f)) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_ref > 0 && !a->ref) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_query > 0 && (!a->query || !a->d2 || !a->index)) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_query > meval::kMaxItems || a->num_ref > meval::kMaxItems) return MGS_ERR_UNSUPPORTED;
+  if (a->num_query > kMaxItems || a->num_ref > kMaxItems) return MGS_ERR_UNSUPPORTED;
   const int P = a->num_query, Q = a->num_ref;
   if (P == 0) return MGS_OK;
   const meval::GridScratch S = meval::grid_scratch_of(a->scratch, (size_t)Q);
   hipStream_t st = (hipStream_t)stream;
   const dim3 th(meval::kThreads), cells(meval::kCellBlocks);
   launch("nn_init", meval::k_nn_init, dim3(1), dim3(64), st, S);
-  if (Q > 0) launch("nn_bbox", meval::k_nn_bbox, dim3(meval::grid_of(Q)), th, st, a->ref, Q, S);
+  if (Q > 0) launch("nn_bbox", meval::k_nn_bbox, dim3(grid_of(Q)), th, st, a->ref, Q, S);
   launch("nn_plan", meval::k_nn_plan, dim3(1), dim3(64), st, S, Q, a->cell_size);
   launch("nn_clear", meval::k_nn_clear, cells, th, st, S);
-  if (Q > 0) launch("nn_count", meval::k_nn_count, dim3(meval::grid_of(Q)), th, st, a->ref, Q, S);
+  if (Q > 0) launch("nn_count", meval::k_nn_count, dim3(grid_of(Q)), th, st, a->ref, Q, S);
   launch("nn_cellscan", meval::k_nn_cellscan, cells, th, st, S);
   launch("nn_scan_totals", meval::k_nn_scan_totals, dim3(1), th, st, S);
   launch("nn_cellstart", meval::k_nn_cellstart, dim3(meval::kCellBlocks + 1), th, st, S);
-  if (Q > 0) launch("nn_scatter", meval::k_nn_scatter, dim3(meval::grid_of(Q)), th, st, a->ref, Q, S);
-  launch("nn_query", meval::k_nn_query, dim3(meval::grid_of(P)), th, st, *a, S);
+  if (Q > 0) launch("nn_scatter", meval::k_nn_scatter, dim3(grid_of(Q)), th, st, a->ref, Q, S);
+  launch("nn_query", meval::k_nn_query, dim3(grid_of(P)), th, st, *a, S);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 static int32_t eval_status(const mgs_mesh_eval_args* a) {
   if (!a || a->num < 0 || !a->scratch) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num > meval::kMaxItems) return MGS_ERR_UNSUPPORTED;
+  if (a->num > kMaxItems) return MGS_ERR_UNSUPPORTED;
   return MGS_OK;
 }
 

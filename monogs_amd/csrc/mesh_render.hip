@@ -10,8 +10,8 @@
 //                  the same shade(): both paths write the same keys
 //   k_mr_resolve   keys -> depth, face_id; record[2] = the length of the list
 //   k_vis          one thread per vertex: seen_count[v] += the view sees it
-//   k_cull_init / k_cull_faces / k_cull_flags / k_compact_scan / k_cull_emit   the cull: face flags and vertex marks, the
-//                  stable compaction of mesh_clean.hip (compact_scan.h)
+//   k_cull_init / k_cull_faces / k_cull_flags   the cull: face flags and vertex marks, their in-block ranks and block totals
+//   k_compact_scan / k_compact_emit             the stable compaction (compact_scan.h)
 //
 // Exactness.  Coverage is integer: the snapped vertices lie within 2^24 of the origin in 1/256 pixel and a tested pixel
 // lies inside the face's box, so every edge function is below 2^51 and converts to fp64 exactly.  Depth is a chain of
@@ -28,6 +28,7 @@
 #include "../../include/monogs_raster.h"
 #include "compact_scan.h"
 #include "launch.h"
+#include "pinhole.h"
 #include "rn_math.h"
 
 namespace mgs {
@@ -35,42 +36,13 @@ namespace mrender {
 
 constexpr int kThreads = 256;
 static_assert(kThreads == kCompactThreads, "block_scan2 scans a workgroup of kCompactThreads");
-constexpr long long kMaxItems = ((1ll << 31) - 1) / 3;    // 3 n < 2^31: 32-bit element indices of [n,3] arrays
 constexpr long long kMaxPixels = (1ll << 31) - 1;
 constexpr float kSnapLimit = 16777216.f;                  // 2^24, in 1/256 pixel
 constexpr unsigned long long kEmptyKey = ~0ull;
 
-__host__ __device__ inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
-static inline int grid_of(long long n) { return (int)((n + kThreads - 1) / kThreads); }
-
-struct Camera {
-  float r[3][4];
-  float fx, fy, cx, cy, z_near;
-};
-
-__device__ __forceinline__ Camera camera_of(const float* __restrict__ T, float fx, float fy, float cx, float cy, float z_near) {
-  Camera c;
-#pragma unroll
-  for (int r = 0; r < 3; r++)
-#pragma unroll
-    for (int k = 0; k < 4; k++) c.r[r][k] = T[4 * r + k];
-  c.fx = fx; c.fy = fy; c.cx = cx; c.cy = cy; c.z_near = z_near;
-  return c;
-}
-
-__device__ __forceinline__ float cam_row(const Camera& c, int r, float px, float py, float pz) {
-  return add_rn(add_rn(add_rn(mul_rn(c.r[r][0], px), mul_rn(c.r[r][1], py)), mul_rn(c.r[r][2], pz)), c.r[r][3]);
-}
-
-// (u, v, zc) of vertex i; false when !(zc > z_near)
-__device__ __forceinline__ bool project(const float* __restrict__ verts, int i, const Camera& c, float& u, float& v, float& zc) {
-  const float px = verts[3 * (size_t)i], py = verts[3 * (size_t)i + 1], pz = verts[3 * (size_t)i + 2];
-  const float xc = cam_row(c, 0, px, py, pz), yc = cam_row(c, 1, px, py, pz);
-  zc = cam_row(c, 2, px, py, pz);
-  if (!(zc > c.z_near)) return false;
-  u = add_rn(mul_rn(c.fx, __fdiv_rn(xc, zc)), c.cx);
-  v = add_rn(mul_rn(c.fy, __fdiv_rn(yc, zc)), c.cy);
-  return true;
+// (u, v, zc) of vertex i (pinhole.h: the TSDF fusion's projection); false when !(zc > z_near)
+__device__ __forceinline__ bool project_vertex(const float* __restrict__ verts, int i, const Pinhole& c, float& u, float& v, float& zc) {
+  return project(c, verts[3 * (size_t)i], verts[3 * (size_t)i + 1], verts[3 * (size_t)i + 2], u, v, zc);
 }
 
 // ---- render -----------------------------------------------------------------------------------------------------------
@@ -80,27 +52,14 @@ struct RenderScratch {
   int* num_large;             // [1]
 };
 
-struct RenderLayout {
-  size_t keys, list, num_large, bytes;
-};
-
-static RenderLayout render_layout(size_t HW, size_t F) {
-  RenderLayout L;
-  size_t o = 0;
-  L.keys = o; o += pad256(8 * HW);
-  L.list = o; o += pad256(4 * F);
-  L.num_large = o; o += 256;
-  L.bytes = o;
-  return L;
-}
-
-static RenderScratch render_scratch(void* p, size_t HW, size_t F) {
-  const RenderLayout L = render_layout(HW, F);
-  char* c = static_cast<char*>(p);
+// the planes of the scratch buffer at p, in their order; *bytes (if given): their size (p may then be null)
+static RenderScratch render_scratch(void* p, size_t HW, size_t F, size_t* bytes = nullptr) {
+  Carver c(p);
   RenderScratch S;
-  S.keys = reinterpret_cast<unsigned long long*>(c + L.keys);
-  S.list = reinterpret_cast<int*>(c + L.list);
-  S.num_large = reinterpret_cast<int*>(c + L.num_large);
+  S.keys = c.take<unsigned long long>(HW);
+  S.list = c.take<int>(F);
+  S.num_large = c.take<int>();
+  if (bytes) *bytes = c.bytes;
   return S;
 }
 
@@ -118,7 +77,7 @@ __device__ __forceinline__ long long edge(long long ax, long long ay, long long 
   return (bx - ax) * (py - ay) - (by - ay) * (px - ax);
 }
 
-__device__ __forceinline__ int setup_face(const mgs_mesh_render_args& A, const Camera& cam, int f, FaceSetup& S) {
+__device__ __forceinline__ int setup_face(const mgs_mesh_render_args& A, const Pinhole& cam, int f, FaceSetup& S) {
   const int V = A.num_verts;
   int idx[3];
 #pragma unroll
@@ -128,7 +87,7 @@ __device__ __forceinline__ int setup_face(const mgs_mesh_render_args& A, const C
 #pragma unroll
   for (int e = 0; e < 3; e++) {
     float u = 0.f, v = 0.f, zc = 0.f;
-    bool good = project(A.verts, idx[e], cam, u, v, zc) && zc <= FLT_MAX;
+    bool good = project_vertex(A.verts, idx[e], cam, u, v, zc) && zc <= FLT_MAX;
     float xs = 0.f, ys = 0.f;
     if (good) {
       xs = rintf(mul_rn(u, 256.f));
@@ -185,7 +144,7 @@ __global__ __launch_bounds__(kThreads) void k_mr_faces(mgs_mesh_render_args A, R
   const int F = A.num_faces;
   int status = kFaceIgnored;
   if (f < F) {
-    const Camera cam = camera_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
+    const Pinhole cam = pinhole_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
     FaceSetup P;
     status = setup_face(A, cam, f, P);
     if (status == kFaceDrawn) {
@@ -209,7 +168,7 @@ __global__ __launch_bounds__(kThreads) void k_mr_faces(mgs_mesh_render_args A, R
 
 __global__ __launch_bounds__(kThreads) void k_mr_large(mgs_mesh_render_args A, RenderScratch S) {
   const int n = min(*S.num_large, A.num_faces);
-  const Camera cam = camera_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
+  const Pinhole cam = pinhole_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
   for (int i = blockIdx.x; i < n; i += gridDim.x) {       // uniform over the workgroup
     const int f = S.list[i];
     if ((unsigned)f >= (unsigned)A.num_faces) continue;
@@ -235,13 +194,12 @@ __global__ __launch_bounds__(kThreads) void k_mr_resolve(mgs_mesh_render_args A,
 __global__ __launch_bounds__(kThreads) void k_vis(mgs_vertex_visibility_args A) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
   if (i >= A.num_verts) return;
-  const Camera cam = camera_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
+  const Pinhole cam = pinhole_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
   float u, v, zc;
-  if (!project(A.verts, i, cam, u, v, zc)) return;
-  const float uf = floorf(add_rn(u, 0.5f)), vf = floorf(add_rn(v, 0.5f));
-  if (!(uf >= 0.f && uf < (float)A.width && vf >= 0.f && vf < (float)A.height)) return;      // false for NaN
+  int x, y;
+  if (!project_vertex(A.verts, i, cam, u, v, zc) || !round_to_pixel(u, v, (float)A.width, (float)A.height, x, y)) return;
   if (A.depth) {
-    const float d = A.depth[(size_t)(int)vf * A.width + (int)uf];
+    const float d = A.depth[(size_t)y * A.width + x];
     if (!(d > 0.f)) {
       if (!A.empty_visible) return;
     } else if (sub_rn(zc, d) > A.eps) {
@@ -258,27 +216,14 @@ struct CullScratch {
   uint4* base;      // [blocks(max(V,F))] x: kept vertices, y: kept faces of the earlier blocks, z: bad faces
 };
 
-struct CullLayout {
-  size_t vrel, frel, base, bytes;
-};
-
-static CullLayout cull_layout(size_t V, size_t F) {
-  CullLayout L;
-  size_t o = 0;
-  L.vrel = o; o += pad256(4 * V);
-  L.frel = o; o += pad256(4 * F);
-  L.base = o; o += pad256(sizeof(uint4) * (size_t)grid_of((long long)(V > F ? V : F)));
-  L.bytes = o > 0 ? o : 256;
-  return L;
-}
-
-static CullScratch cull_scratch(void* p, size_t V, size_t F) {
-  const CullLayout L = cull_layout(V, F);
-  char* c = static_cast<char*>(p);
+// the planes of the scratch buffer at p, in their order; *bytes (if given): their size, never 0 (p may then be null)
+static CullScratch cull_scratch(void* p, size_t V, size_t F, size_t* bytes = nullptr) {
+  Carver c(p);
   CullScratch S;
-  S.vrel = reinterpret_cast<int*>(c + L.vrel);
-  S.frel = reinterpret_cast<int*>(c + L.frel);
-  S.base = reinterpret_cast<uint4*>(c + L.base);
+  S.vrel = c.take<int>(V);
+  S.frel = c.take<int>(F);
+  S.base = c.take<uint4>((size_t)grid_of((long long)(V > F ? V : F)));
+  if (bytes) *bytes = c.bytes > 0 ? c.bytes : 256;
   return S;
 }
 
@@ -316,47 +261,6 @@ __global__ __launch_bounds__(kThreads) void k_cull_flags(CullScratch S, int V, i
   if (threadIdx.x == 0) S.base[blockIdx.x] = make_uint4(tv, tf, bad, 0u);
 }
 
-__global__ __launch_bounds__(kThreads) void k_cull_emit(mgs_mesh_cull_args A, CullScratch S) {
-  const int i = blockIdx.x * kThreads + threadIdx.x;
-  const int V = A.num_verts, F = A.num_faces;
-  if (i < V) {
-    const int r = S.vrel[i];
-    if (r >= 0) {
-      const unsigned id = S.base[i / kThreads].x + (unsigned)r;
-      if (id < (unsigned)A.out_num_verts) {
-#pragma unroll
-        for (int ax = 0; ax < 3; ax++) A.out_verts[3 * (size_t)id + ax] = A.verts[3 * (size_t)i + ax];
-        if (A.colors && A.out_colors) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ch++) A.out_colors[3 * (size_t)id + ch] = A.colors[3 * (size_t)i + ch];
-        }
-      }
-    }
-  }
-  if (i < F) {
-    const int r = S.frel[i];
-    if (r >= 0) {
-      const unsigned fid = S.base[i / kThreads].y + (unsigned)r;
-      if (fid < (unsigned)A.out_num_faces) {
-#pragma unroll
-        for (int e = 0; e < 3; e++) {
-          const int v = A.faces[3 * (size_t)i + e];
-          int id = -1;                                  // only if the faces changed since the count
-          if ((unsigned)v < (unsigned)V) id = (int)S.base[v / kThreads].x + S.vrel[v];
-          A.out_faces[3 * (size_t)fid + e] = id;
-        }
-      }
-    }
-  }
-}
-
-static int32_t cull_status(const mgs_mesh_cull_args* a) {
-  if (!a || a->num_verts < 0 || a->num_faces < 0 || !a->scratch) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_faces > 0 && !a->faces) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_verts > kMaxItems || a->num_faces > kMaxItems) return MGS_ERR_UNSUPPORTED;
-  return MGS_OK;
-}
-
 static bool camera_ok(float fx, float fy, float cx, float cy, float z_near) {
   return fx == fx && fy == fy && cx == cx && cy == cy && z_near == z_near;
 }
@@ -373,9 +277,9 @@ int32_t mgs_vertex_visibility_args_size(void) { return (int32_t)sizeof(mgs_verte
 int32_t mgs_mesh_cull_args_size(void) { return (int32_t)sizeof(mgs_mesh_cull_args); }
 
 uint64_t mgs_mesh_render_scratch_bytes(int32_t height, int32_t width, int32_t num_faces) {
-  if (height < 1 || width < 1 || num_faces < 0 || num_faces > mrender::kMaxItems) return 0;
+  if (height < 1 || width < 1 || num_faces < 0 || num_faces > kMaxItems) return 0;
   if ((long long)height * width > mrender::kMaxPixels) return 0;
-  return mrender::render_layout((size_t)height * (size_t)width, (size_t)num_faces).bytes;
+  return carved_bytes(mrender::render_scratch, (size_t)height * (size_t)width, (size_t)num_faces);
 }
 
 int32_t mgs_mesh_render(const mgs_mesh_render_args* a, void* stream) {
@@ -384,7 +288,7 @@ int32_t mgs_mesh_render(const mgs_mesh_render_args* a, void* stream) {
   if (!a->T || !a->scratch || !a->depth || !a->face_id || !a->record) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_faces > 0 && (!a->faces || (a->num_verts > 0 && !a->verts))) return MGS_ERR_BAD_ARGUMENT;
   if (!mrender::camera_ok(a->fx, a->fy, a->cx, a->cy, a->z_near)) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_verts > mrender::kMaxItems || a->num_faces > mrender::kMaxItems) return MGS_ERR_UNSUPPORTED;
+  if (a->num_verts > kMaxItems || a->num_faces > kMaxItems) return MGS_ERR_UNSUPPORTED;
   const long long HW = (long long)a->height * a->width;
   if (HW > mrender::kMaxPixels) return MGS_ERR_UNSUPPORTED;
   mgs_mesh_render_args A = *a;
@@ -393,12 +297,12 @@ int32_t mgs_mesh_render(const mgs_mesh_render_args* a, void* stream) {
   const mrender::RenderScratch S = mrender::render_scratch(A.scratch, (size_t)HW, (size_t)A.num_faces);
   hipStream_t st = (hipStream_t)stream;
   const dim3 th(mrender::kThreads);
-  launch("mr_fill", mrender::k_mr_fill, dim3(mrender::grid_of(HW)), th, st, S, HW, A.record);
+  launch("mr_fill", mrender::k_mr_fill, dim3(grid_of(HW)), th, st, S, HW, A.record);
   if (A.num_faces > 0) {
-    launch("mr_faces", mrender::k_mr_faces, dim3(mrender::grid_of(A.num_faces)), th, st, A, S);
+    launch("mr_faces", mrender::k_mr_faces, dim3(grid_of(A.num_faces)), th, st, A, S);
     launch("mr_large", mrender::k_mr_large, dim3(A.large_grid), th, st, A, S);
   }
-  launch("mr_resolve", mrender::k_mr_resolve, dim3(mrender::grid_of(HW)), th, st, A, S, HW);
+  launch("mr_resolve", mrender::k_mr_resolve, dim3(grid_of(HW)), th, st, A, S, HW);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
@@ -406,19 +310,19 @@ int32_t mgs_vertex_visibility(const mgs_vertex_visibility_args* a, void* stream)
   if (!a || a->num_verts < 0 || a->width < 1 || a->height < 1 || !a->T) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_verts > 0 && (!a->verts || !a->seen_count)) return MGS_ERR_BAD_ARGUMENT;
   if (!mrender::camera_ok(a->fx, a->fy, a->cx, a->cy, a->z_near) || a->eps != a->eps) return MGS_ERR_BAD_ARGUMENT;
-  if (a->num_verts > mrender::kMaxItems || (long long)a->height * a->width > mrender::kMaxPixels) return MGS_ERR_UNSUPPORTED;
+  if (a->num_verts > kMaxItems || (long long)a->height * a->width > mrender::kMaxPixels) return MGS_ERR_UNSUPPORTED;
   if (a->num_verts == 0) return MGS_OK;
-  launch("mesh_vis", mrender::k_vis, dim3(mrender::grid_of(a->num_verts)), dim3(mrender::kThreads), (hipStream_t)stream, *a);
+  launch("mesh_vis", mrender::k_vis, dim3(grid_of(a->num_verts)), dim3(mrender::kThreads), (hipStream_t)stream, *a);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 uint64_t mgs_mesh_cull_scratch_bytes(int32_t num_verts, int32_t num_faces) {
-  if (num_verts < 0 || num_faces < 0 || num_verts > mrender::kMaxItems || num_faces > mrender::kMaxItems) return 0;
-  return mrender::cull_layout((size_t)num_verts, (size_t)num_faces).bytes;
+  if (num_verts < 0 || num_faces < 0 || num_verts > kMaxItems || num_faces > kMaxItems) return 0;
+  return carved_bytes(mrender::cull_scratch, (size_t)num_verts, (size_t)num_faces);
 }
 
 int32_t mgs_mesh_cull_count(const mgs_mesh_cull_args* a, void* stream) {
-  const int32_t rc = mrender::cull_status(a);
+  const int32_t rc = mesh_sizes_status(a);
   if (rc != MGS_OK) return rc;
   if (!a->counts || (a->rule != 0 && a->rule != 1)) return MGS_ERR_BAD_ARGUMENT;
   if (a->num_verts > 0 && a->num_faces > 0 && !a->seen_count) return MGS_ERR_BAD_ARGUMENT;
@@ -426,26 +330,19 @@ int32_t mgs_mesh_cull_count(const mgs_mesh_cull_args* a, void* stream) {
   const mrender::CullScratch S = mrender::cull_scratch(a->scratch, (size_t)V, (size_t)F);
   hipStream_t st = (hipStream_t)stream;
   const dim3 th(mrender::kThreads);
-  const int blocks = mrender::grid_of(V > F ? V : F);
-  if (V > 0) launch("cull_init", mrender::k_cull_init, dim3(mrender::grid_of(V)), th, st, S, V);
-  if (F > 0) launch("cull_faces", mrender::k_cull_faces, dim3(mrender::grid_of(F)), th, st, *a, S);
+  const int blocks = grid_of(V > F ? V : F);
+  if (V > 0) launch("cull_init", mrender::k_cull_init, dim3(grid_of(V)), th, st, S, V);
+  if (F > 0) launch("cull_faces", mrender::k_cull_faces, dim3(grid_of(F)), th, st, *a, S);
   if (blocks > 0) launch("cull_flags", mrender::k_cull_flags, dim3(blocks), th, st, S, V, F);
   launch("cull_scan", k_compact_scan, dim3(1), th, st, S.base, blocks, a->counts);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 
 int32_t mgs_mesh_cull_emit(const mgs_mesh_cull_args* a, void* stream) {
-  const int32_t rc = mrender::cull_status(a);
+  const int32_t rc = mesh_sizes_status(a);
   if (rc != MGS_OK) return rc;
-  if (a->out_num_verts < 0 || a->out_num_faces < 0) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_verts > a->num_verts || a->out_num_faces > a->num_faces) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_verts == 0 && a->out_num_faces == 0) return MGS_OK;
-  if (a->out_num_verts > 0 && (!a->verts || !a->out_verts || (a->colors && !a->out_colors))) return MGS_ERR_BAD_ARGUMENT;
-  if (a->out_num_faces > 0 && !a->out_faces) return MGS_ERR_BAD_ARGUMENT;
-  const int V = a->num_verts, F = a->num_faces;
-  const mrender::CullScratch S = mrender::cull_scratch(a->scratch, (size_t)V, (size_t)F);
-  launch("cull_emit", mrender::k_cull_emit, dim3(mrender::grid_of(V > F ? V : F)), dim3(mrender::kThreads), (hipStream_t)stream, *a, S);
-  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+  const mrender::CullScratch S = mrender::cull_scratch(a->scratch, (size_t)a->num_verts, (size_t)a->num_faces);
+  return compact_emit("cull_emit", compact_emit_of(*a, S.vrel, S.frel, S.base), (hipStream_t)stream);
 }
 
 }  // extern "C"

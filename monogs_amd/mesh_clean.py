@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._device import compact_numpy, device_colors, device_rows, emit_compacted, stream_ptr, workspace
 
 INFO_KEYS = ("num_clusters", "kept_clusters", "verts_in", "faces_in", "verts_out", "faces_out")
 
@@ -92,40 +93,19 @@ def clean_mesh_numpy(verts, faces, colors=None, keep_largest: Optional[int] = No
     keep_root[kept] = True
     vkeep = keep_root[labels]
     fkeep = keep_root[face_label]
-    new_index = np.cumsum(vkeep) - 1
-    out_f = new_index[f[fkeep]].astype(np.int32).reshape(-1, 3)
     info = dict(num_clusters=int(roots.size), kept_clusters=int(kept.size), verts_in=V, faces_in=F,
                 verts_out=int(vkeep.sum()), faces_out=int(fkeep.sum()))
-    return v[vkeep], out_f, (None if col is None else col[vkeep]), info
+    return compact_numpy(v, f, col, vkeep, fkeep) + (info,)
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------
-_SCRATCH_SLOTS = 4
-_scratch = {}          # (device, V, F) -> (scratch bytes, counts [5] i32); the last _SCRATCH_SLOTS sizes
+_MIRRORS = "clean_mesh_numpy / connected_components_numpy"
 
 
 def _workspace(dev, V, F):
-    key = (str(dev), V, F)
-    ws = _scratch.pop(key, None)
-    if ws is None:
-        nbytes = int(_cabi.lib().mgs_mesh_clean_scratch_bytes(V, F))
-        if nbytes == 0:
-            raise ValueError(f"mesh clean-up: {V} vertices / {F} faces: 3 V and 3 F must stay below 2^31")
-        ws = (torch.empty(nbytes, dtype=torch.uint8, device=dev),
-              torch.zeros(_cabi.MESH_CLEAN_COUNTS, dtype=torch.int32, device=dev))
-        while len(_scratch) >= _SCRATCH_SLOTS:
-            _scratch.pop(next(iter(_scratch)))
-    _scratch[key] = ws          # most recently used last
-    return ws
-
-
-def _device_faces(faces, what):
-    if not torch.is_tensor(faces) or faces.device.type != "cuda":
-        raise RuntimeError(f"{what} runs on the GPU only (HIP kernels, gfx950); the mirrors clean_mesh_numpy / "
-                           "connected_components_numpy run anywhere")
-    if faces.dim() != 2 or faces.shape[1] != 3:
-        raise ValueError(f"{what}: faces must be [F,3], got {tuple(faces.shape)}")
-    return faces.detach().to(torch.int32).contiguous()
+    """(scratch bytes, counts [5] i32)"""
+    return workspace("clean", dev, (V, F), _cabi.lib().mgs_mesh_clean_scratch_bytes,
+                     f"mesh clean-up: {V} vertices / {F} faces: 3 V and 3 F must stay below 2^31", _cabi.MESH_CLEAN_COUNTS)
 
 
 def _args(V, faces, scratch):
@@ -136,14 +116,10 @@ def _args(V, faces, scratch):
     return a
 
 
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
 def connected_components(num_verts: int, faces) -> torch.Tensor:
     """labels [V] i32 on the device of `faces` [F,3]: the smallest vertex index of each vertex's component.  Three
     launches, no host read; indices outside [0,V) connect nothing."""
-    faces = _device_faces(faces, "connected_components")
+    faces = device_rows(faces, "connected_components", "faces", _MIRRORS, torch.int32)
     V, dev = int(num_verts), faces.device
     if V < 0:
         raise ValueError("connected_components: num_verts must be >= 0")
@@ -151,7 +127,7 @@ def connected_components(num_verts: int, faces) -> torch.Tensor:
     labels = torch.empty(V, dtype=torch.int32, device=dev)
     a = _args(V, faces, scratch)
     a.labels = labels.data_ptr() if V else None
-    _cabi.check(_cabi.lib().mgs_mesh_components(C.byref(a), _stream(dev)), "mgs_mesh_components")
+    _cabi.check(_cabi.lib().mgs_mesh_components(C.byref(a), stream_ptr(dev)), "mgs_mesh_components")
     return labels
 
 
@@ -160,36 +136,23 @@ def clean_mesh(verts, faces, colors=None, keep_largest: Optional[int] = None, mi
     by size (module docstring), everything else dropped and the rest compacted in order.  One host read, of the counts
     record, between the scan and the emission; a face with an index outside [0,V) raises ValueError after it."""
     keep_largest, min_faces = _check_params(keep_largest, min_faces)
-    faces = _device_faces(faces, "clean_mesh")
+    faces = device_rows(faces, "clean_mesh", "faces", _MIRRORS, torch.int32)
     dev = faces.device
     if not torch.is_tensor(verts) or verts.device != dev or verts.dim() != 2 or verts.shape[1] != 3:
         raise ValueError("clean_mesh: verts must be [V,3] on the device of faces")
     verts = verts.detach().to(torch.float32).contiguous()
     V, F = int(verts.shape[0]), int(faces.shape[0])
-    if colors is not None:
-        if not torch.is_tensor(colors) or colors.device != dev or tuple(colors.shape) != (V, 3):
-            raise ValueError(f"clean_mesh: colors must be [{V},3] on the device of faces")
-        colors = colors.detach().to(torch.float32).contiguous()
+    colors = device_colors(colors, "clean_mesh", V, dev)
     L = _cabi.lib()
     scratch, counts = _workspace(dev, V, F)
     a = _args(V, faces, scratch)
     a.keep_largest = -1 if keep_largest is None else min(keep_largest, 2 ** 31 - 1)
     a.min_faces = min(min_faces, 2 ** 31 - 1)
     a.counts = counts.data_ptr()
-    _cabi.check(L.mgs_mesh_clean_count(C.byref(a), _stream(dev)), "mgs_mesh_clean_count")
+    _cabi.check(L.mgs_mesh_clean_count(C.byref(a), stream_ptr(dev)), "mgs_mesh_clean_count")
     V2, F2, clusters, kept, bad = (int(c) for c in counts.cpu())
     if bad:
         raise ValueError(f"clean_mesh: {bad} of {F} faces hold an index outside [0, {V})")
-    out_v = torch.empty(V2, 3, device=dev)
-    out_f = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    out_c = None if colors is None else torch.empty(V2, 3, device=dev)
-    a.out_num_verts, a.out_num_faces = V2, F2
-    if V2:
-        a.verts, a.out_verts = verts.data_ptr(), out_v.data_ptr()
-        if colors is not None:
-            a.colors, a.out_colors = colors.data_ptr(), out_c.data_ptr()
-    if F2:
-        a.out_faces = out_f.data_ptr()
-    _cabi.check(L.mgs_mesh_clean_emit(C.byref(a), _stream(dev)), "mgs_mesh_clean_emit")
+    out_v, out_f, out_c = emit_compacted(a, L.mgs_mesh_clean_emit, "mgs_mesh_clean_emit", verts, colors, V2, F2)
     info = dict(num_clusters=clusters, kept_clusters=kept, verts_in=V, faces_in=F, verts_out=V2, faces_out=F2)
     return out_v, out_f, out_c, info

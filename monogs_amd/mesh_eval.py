@@ -26,6 +26,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._device import device_rows, ptr as _ptr, stream_ptr, workspace
 
 METRIC_KEYS = ("accuracy", "completion", "chamfer", "precision", "recall", "completion_ratio", "f_score", "hausdorff",
                "n_pred", "n_gt", "bad_faces")
@@ -245,43 +246,15 @@ def evaluate_mesh_numpy(pred, gt, n_samples: int = 200_000, threshold: float = 0
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------
-_SCRATCH_SLOTS = 4
-_scratch = {}          # (kind, device, size) -> scratch bytes; the last _SCRATCH_SLOTS
+_MIRRORS = "sample_surface_numpy / nearest_distance_torch / evaluate_mesh_numpy"
 
 
 def _workspace(kind, dev, size, nbytes_fn, what):
-    key = (kind, str(dev), size)
-    ws = _scratch.pop(key, None)
-    if ws is None:
-        nbytes = int(nbytes_fn())
-        if nbytes == 0:
-            raise ValueError(f"{what}: {size} items: 3 n must stay below 2^31")
-        ws = torch.empty(nbytes, dtype=torch.uint8, device=dev)
-        while len(_scratch) >= _SCRATCH_SLOTS:
-            _scratch.pop(next(iter(_scratch)))
-    _scratch[key] = ws          # most recently used last
-    return ws
+    return workspace(kind, dev, size, nbytes_fn, f"{what}: {size} items: 3 n must stay below 2^31")[0]
 
 
 def _device_points(t, what, name, dev=None):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise RuntimeError(f"{what} runs on the GPU only (HIP kernels, gfx950); the mirrors sample_surface_numpy / "
-                           "nearest_distance_torch / evaluate_mesh_numpy run anywhere")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{what}: {name} must be on {dev}")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"{what}: {name} must be [n,3], got {tuple(t.shape)}")
-    if t.shape[0] > _cabi.MESH_EVAL_MAX_ITEMS:
-        raise ValueError(f"{what}: {name} has {t.shape[0]} rows: 3 n must stay below 2^31")
-    return t
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
+    return device_rows(t, what, name, _MIRRORS, dev=dev)
 
 
 def sample_surface(verts, faces, n: int, seed: int = 0, randoms=None, with_record: bool = False):
@@ -306,12 +279,12 @@ def sample_surface(verts, faces, n: int, seed: int = 0, randoms=None, with_recor
         randoms = randoms.detach().to(torch.int64).to(torch.int32).contiguous()      # the low 32 bits
         a.randoms = _ptr(randoms)
     L = _cabi.lib()
-    scratch = _workspace("sample", dev, F, lambda: L.mgs_surface_sample_scratch_bytes(F), what)
+    scratch = _workspace("sample", dev, (F,), L.mgs_surface_sample_scratch_bytes, what)
     points = torch.empty(n, 3, dtype=torch.float32, device=dev)
     face_index = torch.empty(n, dtype=torch.int32, device=dev)
     record = torch.empty(_cabi.SAMPLE_RECORD_INTS, dtype=torch.int32, device=dev)
     a.scratch, a.points, a.face_index, a.record = scratch.data_ptr(), _ptr(points), _ptr(face_index), record.data_ptr()
-    _cabi.check(L.mgs_surface_sample(C.byref(a), _stream(dev)), "mgs_surface_sample")
+    _cabi.check(L.mgs_surface_sample(C.byref(a), stream_ptr(dev)), "mgs_surface_sample")
     return (points, face_index, record) if with_record else (points, face_index)
 
 
@@ -329,13 +302,13 @@ def nearest_distance(query, ref, cell_size=None):
             raise ValueError(f"{what}: cell_size must be None or a positive number, got {cell_size}")
     P, Q = int(query.shape[0]), int(ref.shape[0])
     L = _cabi.lib()
-    scratch = _workspace("nearest", dev, Q, lambda: L.mgs_nearest_scratch_bytes(Q), what)
+    scratch = _workspace("nearest", dev, (Q,), L.mgs_nearest_scratch_bytes, what)
     d2 = torch.empty(P, dtype=torch.float32, device=dev)
     index = torch.empty(P, dtype=torch.int32, device=dev)
     a = _cabi.NearestArgs()
     a.num_query, a.num_ref, a.cell_size = P, Q, h
     a.query, a.ref, a.scratch, a.d2, a.index = _ptr(query), _ptr(ref), scratch.data_ptr(), _ptr(d2), _ptr(index)
-    _cabi.check(L.mgs_nearest_distance(C.byref(a), _stream(dev)), "mgs_nearest_distance")
+    _cabi.check(L.mgs_nearest_distance(C.byref(a), stream_ptr(dev)), "mgs_nearest_distance")
     return d2, index
 
 
@@ -350,7 +323,7 @@ def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_record
     if not thr >= 0.0:
         raise ValueError(f"{what}: threshold must be >= 0, got {threshold}")
     L = _cabi.lib()
-    scratch = _workspace("stats", dev, 0, L.mgs_mesh_eval_scratch_bytes, what)
+    scratch = _workspace("stats", dev, (), L.mgs_mesh_eval_scratch_bytes, what)
     record = torch.empty(_cabi.MESH_EVAL_RECORD_DOUBLES, dtype=torch.float64, device=dev)
     a = _cabi.MeshEvalArgs()
     a.threshold, a.scratch, a.record = thr, scratch.data_ptr(), record.data_ptr()
@@ -359,10 +332,10 @@ def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_record
         t = t.detach().to(device=dev, dtype=torch.float32).contiguous().reshape(-1)
         keep.append(t)
         a.num, a.direction, a.d2 = int(t.shape[0]), d, _ptr(t)
-        _cabi.check(L.mgs_mesh_eval_stats(C.byref(a), _stream(dev)), "mgs_mesh_eval_stats")
+        _cabi.check(L.mgs_mesh_eval_stats(C.byref(a), stream_ptr(dev)), "mgs_mesh_eval_stats")
     for d, r in enumerate(sample_records):
         a.sample_record[d] = None if r is None else r.data_ptr()
-    _cabi.check(L.mgs_mesh_eval_finish(C.byref(a), _stream(dev)), "mgs_mesh_eval_finish")
+    _cabi.check(L.mgs_mesh_eval_finish(C.byref(a), stream_ptr(dev)), "mgs_mesh_eval_finish")
     return record
 
 

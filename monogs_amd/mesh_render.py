@@ -32,6 +32,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._device import compact_numpy, device_colors, device_rows, emit_compacted, ptr as _ptr, stream_ptr, workspace
 
 RULES = ("all", "any")
 SNAP_LIMIT = float(2 ** 24)          # |X|, |Y| of a snapped vertex, in 1/256 pixel
@@ -193,37 +194,17 @@ def cull_mesh_numpy(verts, faces, colors=None, seen_count=None, min_views: int =
     fkeep = valid & (ok.any(axis=1) if any_rule else ok.all(axis=1))
     vkeep = np.zeros(V, bool)
     vkeep[f[fkeep].reshape(-1)] = True
-    new_index = np.cumsum(vkeep) - 1
-    out_f = new_index[f[fkeep]].astype(np.int32).reshape(-1, 3)
     info = dict(verts_in=V, faces_in=F, verts_out=int(vkeep.sum()), faces_out=int(fkeep.sum()),
                 bad_faces=int((~valid).sum()))
-    return v[vkeep], out_f, (None if col is None else col[vkeep]), info
+    return compact_numpy(v, f, col, vkeep, fkeep) + (info,)
 
 
 # ---- the device ------------------------------------------------------------------------------------------------------
-_SCRATCH_SLOTS = 4
-_scratch = {}          # (kind, device, sizes) -> scratch tensors; the last _SCRATCH_SLOTS
-
-
-def _workspace(key, make):
-    ws = _scratch.pop(key, None)
-    if ws is None:
-        ws = make()
-        while len(_scratch) >= _SCRATCH_SLOTS:
-            _scratch.pop(next(iter(_scratch)))
-    _scratch[key] = ws          # most recently used last
-    return ws
+_MIRRORS = "render_mesh_depth_numpy / vertex_visibility_torch / cull_mesh_numpy"
 
 
 def _device_rows(t, what, name, dtype, dev=None):
-    if not torch.is_tensor(t) or t.device.type != "cuda":
-        raise RuntimeError(f"{what} runs on the GPU only (HIP kernels, gfx950); the mirrors render_mesh_depth_numpy / "
-                           "vertex_visibility_torch / cull_mesh_numpy run anywhere")
-    if dev is not None and t.device != dev:
-        raise ValueError(f"{what}: {name} must be on {dev}")
-    if t.dim() != 2 or t.shape[1] != 3:
-        raise ValueError(f"{what}: {name} must be [n,3], got {tuple(t.shape)}")
-    return t.detach().to(dtype).contiguous()
+    return device_rows(t, what, name, _MIRRORS, dtype, dev)
 
 
 def _device_pose(T, what, dev):
@@ -231,14 +212,6 @@ def _device_pose(T, what, dev):
     if tuple(T.shape) != (4, 4):
         raise ValueError(f"{what}: T_w2c must be [4,4], got {tuple(T.shape)}")
     return T.to(dev, torch.float32).contiguous()
-
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
-
-
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
 
 
 def render_mesh_depth(verts, faces, T_w2c, fx, fy, cx, cy, H, W, z_near: float = 0.2,
@@ -260,8 +233,8 @@ def render_mesh_depth(verts, faces, T_w2c, fx, fy, cx, cy, H, W, z_near: float =
         raise ValueError(f"{what}: large_threshold must be >= 0 and large_grid >= 1")
     T = _device_pose(T_w2c, what, dev)
     L = _cabi.lib()
-    scratch = _workspace(("render", str(dev), H, W, F), lambda: torch.empty(
-        int(L.mgs_mesh_render_scratch_bytes(H, W, F)), dtype=torch.uint8, device=dev))
+    scratch, _ = workspace("render", dev, (H, W, F), L.mgs_mesh_render_scratch_bytes,
+                           f"{what}: {H} x {W} pixels / {F} faces: H W and 3 F must stay below 2^31")
     depth = torch.empty(H, W, dtype=torch.float32, device=dev)
     face_id = torch.empty(H, W, dtype=torch.int32, device=dev)
     record = torch.empty(_cabi.MESH_RENDER_RECORD_INTS, dtype=torch.int32, device=dev)
@@ -271,7 +244,7 @@ def render_mesh_depth(verts, faces, T_w2c, fx, fy, cx, cy, H, W, z_near: float =
     a.fx, a.fy, a.cx, a.cy, a.z_near = float(fx), float(fy), float(cx), float(cy), float(z_near)
     a.verts, a.faces, a.T, a.scratch = _ptr(verts), _ptr(faces), T.data_ptr(), scratch.data_ptr()
     a.depth, a.face_id, a.record = depth.data_ptr(), face_id.data_ptr(), record.data_ptr()
-    _cabi.check(L.mgs_mesh_render(C.byref(a), _stream(dev)), "mgs_mesh_render")
+    _cabi.check(L.mgs_mesh_render(C.byref(a), stream_ptr(dev)), "mgs_mesh_render")
     return depth, face_id, record
 
 
@@ -303,7 +276,7 @@ def vertex_visibility(verts, T_w2c, fx, fy, cx, cy, H, W, depth=None, eps: float
     a.num_verts, a.width, a.height, a.empty_visible = V, W, H, 1 if empty_visible else 0
     a.fx, a.fy, a.cx, a.cy, a.z_near, a.eps = float(fx), float(fy), float(cx), float(cy), float(z_near), float(eps)
     a.verts, a.T, a.depth, a.seen_count = _ptr(verts), T.data_ptr(), (None if depth is None else depth.data_ptr()), _ptr(out)
-    _cabi.check(_cabi.lib().mgs_vertex_visibility(C.byref(a), _stream(dev)), "mgs_vertex_visibility")
+    _cabi.check(_cabi.lib().mgs_vertex_visibility(C.byref(a), stream_ptr(dev)), "mgs_vertex_visibility")
     return out
 
 
@@ -322,31 +295,17 @@ def cull_mesh(verts, faces, colors=None, seen_count=None, min_views: int = 1, ru
     if not torch.is_tensor(seen_count) or seen_count.device != dev or tuple(seen_count.shape) != (V,):
         raise ValueError(f"{what}: seen_count must be [{V}] on the device of faces")
     seen_count = seen_count.detach().to(torch.int32).contiguous()
-    if colors is not None:
-        if not torch.is_tensor(colors) or colors.device != dev or tuple(colors.shape) != (V, 3):
-            raise ValueError(f"{what}: colors must be [{V},3] on the device of faces")
-        colors = colors.detach().to(torch.float32).contiguous()
+    colors = device_colors(colors, what, V, dev)
     L = _cabi.lib()
-    scratch, counts = _workspace(("cull", str(dev), V, F), lambda: (
-        torch.empty(int(L.mgs_mesh_cull_scratch_bytes(V, F)), dtype=torch.uint8, device=dev),
-        torch.zeros(_cabi.MESH_CULL_COUNTS, dtype=torch.int32, device=dev)))
+    scratch, counts = workspace("cull", dev, (V, F), L.mgs_mesh_cull_scratch_bytes,
+                                f"{what}: {V} vertices / {F} faces: 3 V and 3 F must stay below 2^31", _cabi.MESH_CULL_COUNTS)
     a = _cabi.MeshCullArgs()
     a.num_verts, a.num_faces, a.rule = V, F, any_rule
     a.min_views = max(-2 ** 31, min(min_views, 2 ** 31 - 1))
     a.faces, a.seen_count, a.scratch, a.counts = _ptr(faces), _ptr(seen_count), scratch.data_ptr(), counts.data_ptr()
-    _cabi.check(L.mgs_mesh_cull_count(C.byref(a), _stream(dev)), "mgs_mesh_cull_count")
+    _cabi.check(L.mgs_mesh_cull_count(C.byref(a), stream_ptr(dev)), "mgs_mesh_cull_count")
     V2, F2, bad, _ = (int(c) for c in counts.cpu())              # the one host read
-    out_v = torch.empty(V2, 3, device=dev)
-    out_f = torch.empty(F2, 3, dtype=torch.int32, device=dev)
-    out_c = None if colors is None else torch.empty(V2, 3, device=dev)
-    a.out_num_verts, a.out_num_faces = V2, F2
-    if V2:
-        a.verts, a.out_verts = verts.data_ptr(), out_v.data_ptr()
-        if colors is not None:
-            a.colors, a.out_colors = colors.data_ptr(), out_c.data_ptr()
-    if F2:
-        a.out_faces = out_f.data_ptr()
-    _cabi.check(L.mgs_mesh_cull_emit(C.byref(a), _stream(dev)), "mgs_mesh_cull_emit")
+    out_v, out_f, out_c = emit_compacted(a, L.mgs_mesh_cull_emit, "mgs_mesh_cull_emit", verts, colors, V2, F2)
     return out_v, out_f, out_c, dict(verts_in=V, faces_in=F, verts_out=V2, faces_out=F2, bad_faces=bad)
 
 

@@ -25,6 +25,7 @@ import numpy as np
 import torch
 
 from . import _cabi
+from ._device import stream_ptr
 
 # the 7 edges a lattice point owns, as offsets (dx, dy, dz) in slot order, and the same as corner codes (bit 0 x ...)
 SLOT_OFFSETS = ((1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 1, 0), (1, 0, 1), (0, 1, 1), (1, 1, 1))
@@ -258,9 +259,6 @@ class TSDFVolume:
         self.weight.zero_()
         self.color.zero_()
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.dev).cuda_stream)
-
     def _plane(self, t, shape, what):
         if t.device != self.dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
             raise ValueError(f"TSDFVolume.{what} must be a contiguous fp32 tensor {shape} on {self.dev}")
@@ -303,7 +301,7 @@ class TSDFVolume:
         a.tsdf, a.wsum = self._plane(self.tsdf, shape, "tsdf"), self._plane(self.weight, shape, "weight")
         a.color = self._plane(self.color, (3,) + shape, "color")
         # `keep` holds the converted inputs until the launch is enqueued; the allocator orders their reuse on this stream
-        _cabi.check(_cabi.lib().mgs_tsdf_integrate(C.byref(a), self._stream()), "mgs_tsdf_integrate")
+        _cabi.check(_cabi.lib().mgs_tsdf_integrate(C.byref(a), stream_ptr(self.dev)), "mgs_tsdf_integrate")
         del keep
 
     def _surface_viewer(self, gaussians, background, H, W):
@@ -375,7 +373,7 @@ class TSDFVolume:
         more host read); None leaves it as extracted."""
         L = _cabi.lib()
         a = self._mesh_args(min_weight)
-        _cabi.check(L.mgs_tsdf_mesh_count(C.byref(a), self._stream()), "mgs_tsdf_mesh_count")
+        _cabi.check(L.mgs_tsdf_mesh_count(C.byref(a), stream_ptr(self.dev)), "mgs_tsdf_mesh_count")
         V, F = (int(v) for v in self._counts.cpu())
         if V == 2 ** 31 - 1 or F > (2 ** 31 - 1) // 3:
             raise ValueError("TSDFVolume.extract_mesh: the mesh exceeds 32-bit indices")
@@ -387,7 +385,7 @@ class TSDFVolume:
             a.verts, a.colors = verts.data_ptr(), colors.data_ptr()
         if F:
             a.faces = faces.data_ptr()
-        _cabi.check(L.mgs_tsdf_mesh_emit(C.byref(a), self._stream()), "mgs_tsdf_mesh_emit")
+        _cabi.check(L.mgs_tsdf_mesh_emit(C.byref(a), stream_ptr(self.dev)), "mgs_tsdf_mesh_emit")
         if clean is not None:
             from .mesh_clean import clean_mesh
             verts, faces, colors, _ = clean_mesh(verts, faces, colors, **clean)

@@ -164,6 +164,41 @@ def test_cull_mesh_equals_the_mirror_bit_for_bit(built, param):
     assert cull_mesh(v, f, None, seen_count=dseen, min_views=min_views, rule=rule)[2] is None
 
 
+def test_cull_mesh_across_a_scan_trip(built):
+    """V = 262 250 and F = 262 188 are 1025 block totals each: the one-workgroup scan takes a second trip, and kept
+    vertices and faces lie on both sides of element 262 144, where it begins."""
+    import mesh_clean_cases as MC
+    from monogs_amd.mesh_render import cull_mesh, cull_mesh_numpy
+    hv, col, hf = MC.two_scan_trips()
+    V, F, trip = hv.shape[0], hf.shape[0], 1024 * 256
+    assert (V, F) == (262250, 262188)
+    seen = np.random.default_rng(0).integers(0, 3, V).astype(np.int32)
+    dv, dc, dseen = (torch.from_numpy(t).to(_dev()) for t in (hv, col, seen))
+
+    def check(faces, rule, min_views, calls):
+        want = cull_mesh_numpy(hv, faces, col, seen_count=seen, min_views=min_views, rule=rule)
+        df = torch.from_numpy(faces).to(_dev())
+        for _ in range(calls):
+            gv, gf, gc, info = cull_mesh(dv, df, dc, seen_count=dseen, min_views=min_views, rule=rule)
+            assert info == want[3]
+            assert np.array_equal(bits(gv), want[0].view(np.int32)) and np.array_equal(bits(gc), want[2].view(np.int32))
+            assert gf.dtype == torch.int32 and np.array_equal(gf.cpu().numpy(), want[1])
+        return want[3]
+
+    for rule, min_views in (("all", 1), ("any", 2)):
+        info = check(hf, rule, min_views, 2)                            # two calls, the same bytes
+        ok = (seen >= min_views)[hf]                                    # the mirror's flags, held to its counts
+        fkeep = ok.any(axis=1) if rule == "any" else ok.all(axis=1)
+        vkeep = np.zeros(V, bool)
+        vkeep[hf[fkeep].reshape(-1)] = True
+        assert (int(fkeep.sum()), int(vkeep.sum())) == (info["faces_out"], info["verts_out"])
+        assert fkeep[trip:].sum() >= 10 and vkeep[trip:].sum() >= 30
+        assert fkeep[:trip].sum() >= 10 and vkeep[:trip].sum() >= 30
+    bad = hf.copy()
+    bad[7, 0] = bad[262150, 1] = V                                      # one bad face on each side of the trip boundary
+    assert check(bad, "any", 2, 1)["bad_faces"] == 2
+
+
 def test_cull_mesh_edges(built):
     from monogs_amd.mesh_render import cull_mesh, cull_mesh_numpy
     dev = _dev()
