@@ -1768,6 +1768,117 @@ uint64_t mgs_mesh_cull_scratch_bytes(int32_t num_verts, int32_t num_faces);
 int32_t mgs_mesh_cull_count(const mgs_mesh_cull_args* args, void* stream);
 int32_t mgs_mesh_cull_emit(const mgs_mesh_cull_args* args, void* stream);
 
+/* ---- mesh normals ("Mesh normals") -----------------------------------------------------------------------
+ * Normals of faces and of vertices, the normal-consistency sums of a mesh evaluation, and the last step from a rendered
+ * face-id plane to a uint8 frame.  Every output is an integer or a single IEEE rounding and independent of the
+ * execution order; the mirrors in monogs_amd/mesh_normals.py and monogs_amd/mesh_render.py are the contract and the
+ * device equals them bit for bit.
+ *
+ * Cross product (all of them; the sampler's): e = b - a, g = c - a, c = (e.y g.z - e.z g.y, e.z g.x - e.x g.z,
+ *   e.x g.y - e.y g.x), every product and difference one fp32 rounding.  A face with an index outside [0,V) is BAD:
+ *   counted in record[0], and it has no cross product.
+ *
+ * mgs_face_normals   normals [F,3]: L = sqrt((cx^2 + cy^2) + cz^2), the root correctly rounded; n = c / L by the
+ *   correctly rounded division.  A face whose L is 0 or not finite is DEGENERATE: counted in record[1].  Bad and
+ *   degenerate faces get (0,0,0).  One launch, one lane per face; `scratch` is not used.
+ *
+ * mgs_vertex_normals   normals [V,3]: the direction of the sum of the cross products of the faces that name the vertex
+ *   (a face counts once per corner), i.e. the area-weighted normal, in fixed point.  A face with a non-finite component,
+ *   or with c = (0,0,0), is DEGENERATE (record[1]) and left out.
+ *     launch 1   M = the largest |component| over the other faces (an integer maximum over bit patterns); E = its
+ *                binary exponent.
+ *     launch 2   q = trunc(c 2^(30 - E)) per component, the product exact in fp64, truncated toward zero: |q| < 2^31;
+ *                q is added to the int64[3] sums of the face's three corners by 64-bit integer atomics - exact in any
+ *                order, and below 2^62 for every F < 2^31.
+ *     launch 3   s = (double)sum; n = (float)(s / sqrt((sx^2 + sy^2) + sz^2)), every operation one fp64 rounding;
+ *                (0,0,0) where the sum is zero: a vertex no usable face names, faces that cancel, M = 0.
+ *   A face whose cross product is below 2^-30 of the largest contributes nothing (the sampler's rule for areas).
+ *   `scratch`: mgs_vertex_normals_scratch_bytes(num_verts), no initial state.
+ *
+ * mgs_mesh_eval_normal_stats   one direction (0: pred -> gt, 1: gt -> pred).  Sample i lies on face `face[i]` of its
+ *   mesh and has the neighbour index[i] at squared distance d2[i], which lies on face ref_face[index[i]] of the other.
+ *   With n, m the two face normals: t = (n.x m.x + n.y m.y) + n.z m.z, every operation one fp32 rounding.  The pair is
+ *   SKIPPED, and counted, when index[i] or either face index is out of range, d2[i] is not finite, or either normal is
+ *   (0,0,0).  Per-workgroup partials in `scratch`: pairs, the fp64 sum of |t|, pairs with t < 0, skipped pairs.
+ * mgs_mesh_eval_normal_finish  after both directions: ONE workgroup adds the partials in a fixed order into `record`
+ *   [MGS_MESH_EVAL_NORMAL_DOUBLES] f64 on the device: {pairs, sum |t|, pairs with t < 0, skipped} of direction 0, of
+ *   direction 1.  monogs_amd.mesh_eval passes the tail of a buffer whose head is mgs_mesh_eval_finish's record.
+ *
+ * mgs_mesh_shade   out [H,W,3] u8 from face_id [H,W] (mgs_mesh_render's); one launch, one lane per pixel.  A pixel with
+ *   a face id outside [0,F) gets `background`.  Every channel is quantised as MGS_VIEW_RGB does: (uint8)(clamp(x, 0, 1)
+ *   255), truncated.  With R the rotation of T and n the face's normal (face_normal [F,3]), n_c = R n per row as
+ *   (r0 n.x + r1 n.y) + r2 n.z:
+ *     MGS_MESH_SHADE_SHADED   grey I = 0.25 + 0.75 |n_c.z|: a two-sided headlight.
+ *     MGS_MESH_SHADE_NORMAL   0.5 n_c + 0.5 with n_c turned to face the camera, as mgs_depth_normal's normals do: with
+ *                             the pixel's ray r = ((x - cx) / fx, (y - cy) / fy, 1), n_c is negated when
+ *                             (n_c.x r.x + n_c.y r.y) + n_c.z > 0.  A (0,0,0) normal is mid-grey.
+ *     MGS_MESH_SHADE_COLOR    the face is set up again as mgs_mesh_render does (projection, snap, int64 edge functions
+ *                             at the pixel centre); t_i = w_i iz_i, c = ((t0 c0 + t1 c1) + t2 c2) / ((t0 + t1) + t2),
+ *                             every operation one fp64 rounding, then one conversion to fp32.  colors [V,3] is fp32, or
+ *                             uint8 (colors_u8 = 1), which is divided by 255 in fp32 first.  A face that cannot be set
+ *                             up (it was not drawn by mgs_mesh_render) gets `background`.
+ *     MGS_MESH_SHADE_MASK     writes `background` where there is no face and nothing elsewhere: the depth view is
+ *                             mgs_view_compose(MGS_VIEW_DEPTH) of the rendered depth, then this.
+ *
+ * A null struct or needed array, a negative size, H or W < 1, a direction outside {0, 1}, a mode outside the four:
+ * MGS_ERR_BAD_ARGUMENT.  3 V, 3 F, 3 n >= 2^31 or 3 H W >= 2^31: MGS_ERR_UNSUPPORTED, and scratch_bytes is 0.  Sizes of 0
+ * are legal.  A refused call launches nothing and writes nothing. */
+#define MGS_MESH_NORMAL_RECORD_INTS 2
+#define MGS_MESH_EVAL_NORMAL_DOUBLES 8
+#define MGS_MESH_SHADE_SHADED 0
+#define MGS_MESH_SHADE_NORMAL 1
+#define MGS_MESH_SHADE_COLOR 2
+#define MGS_MESH_SHADE_MASK 3
+
+typedef struct mgs_mesh_normals_args {
+  int32_t num_verts, num_faces;
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3] */
+  void* scratch;             /* mgs_vertex_normals_scratch_bytes(num_verts) (vertex normals only) */
+  float* normals;            /* [F,3] (face normals) or [V,3] (vertex normals) out */
+  int32_t* record;           /* [MGS_MESH_NORMAL_RECORD_INTS] device out: bad faces, degenerate faces */
+} mgs_mesh_normals_args;
+
+typedef struct mgs_mesh_eval_normal_args {
+  int32_t num, num_ref;              /* samples of this direction's mesh, and of the other */
+  int32_t num_faces, num_ref_faces;  /* faces of the two meshes */
+  int32_t direction, reserved0;
+  const float* d2;                   /* [num] (stats only) */
+  const int32_t* index;              /* [num] neighbour among the other mesh's samples (stats only) */
+  const int32_t* face;               /* [num] face of every sample (stats only) */
+  const int32_t* ref_face;           /* [num_ref] face of every sample of the other mesh (stats only) */
+  const float* normals;              /* [num_faces,3] (stats only) */
+  const float* ref_normals;          /* [num_ref_faces,3] (stats only) */
+  void* scratch;                     /* mgs_mesh_eval_normal_scratch_bytes() */
+  double* record;                    /* [MGS_MESH_EVAL_NORMAL_DOUBLES] device (finish only) */
+} mgs_mesh_eval_normal_args;
+
+typedef struct mgs_mesh_shade_args {
+  int32_t num_verts, num_faces, width, height;
+  int32_t mode;              /* MGS_MESH_SHADE_* */
+  int32_t colors_u8;         /* 1: colors is uint8 [V,3] */
+  float fx, fy, cx, cy, z_near;
+  uint8_t background[4];     /* r, g, b, spare */
+  const float* verts;        /* [V,3] (COLOR) */
+  const int32_t* faces;      /* [F,3] (COLOR) */
+  const float* T;            /* [4,4] device (all but MASK) */
+  const int32_t* face_id;    /* [H,W] */
+  const float* face_normal;  /* [F,3] (SHADED, NORMAL) */
+  const void* colors;        /* [V,3] f32 or u8 (COLOR) */
+  uint8_t* out;              /* [H,W,3] */
+} mgs_mesh_shade_args;
+
+int32_t mgs_mesh_normals_args_size(void);
+uint64_t mgs_vertex_normals_scratch_bytes(int32_t num_verts);
+int32_t mgs_face_normals(const mgs_mesh_normals_args* args, void* stream);
+int32_t mgs_vertex_normals(const mgs_mesh_normals_args* args, void* stream);
+int32_t mgs_mesh_eval_normal_args_size(void);
+uint64_t mgs_mesh_eval_normal_scratch_bytes(void);
+int32_t mgs_mesh_eval_normal_stats(const mgs_mesh_eval_normal_args* args, void* stream);
+int32_t mgs_mesh_eval_normal_finish(const mgs_mesh_eval_normal_args* args, void* stream);
+int32_t mgs_mesh_shade_args_size(void);
+int32_t mgs_mesh_shade(const mgs_mesh_shade_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

@@ -52,6 +52,9 @@ EXPORTS = (
     "mgs_mesh_render_args_size", "mgs_mesh_render_scratch_bytes", "mgs_mesh_render",
     "mgs_vertex_visibility_args_size", "mgs_vertex_visibility",
     "mgs_mesh_cull_args_size", "mgs_mesh_cull_scratch_bytes", "mgs_mesh_cull_count", "mgs_mesh_cull_emit",
+    "mgs_mesh_normals_args_size", "mgs_vertex_normals_scratch_bytes", "mgs_face_normals", "mgs_vertex_normals",
+    "mgs_mesh_eval_normal_args_size", "mgs_mesh_eval_normal_scratch_bytes", "mgs_mesh_eval_normal_stats",
+    "mgs_mesh_eval_normal_finish", "mgs_mesh_shade_args_size", "mgs_mesh_shade",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -451,6 +454,27 @@ class MeshCullArgs(C.Structure):
                 + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
 
 
+MESH_NORMAL_RECORD_INTS = 2                   # MGS_MESH_NORMAL_RECORD_INTS: bad faces, degenerate faces
+MESH_EVAL_NORMAL_DOUBLES = 8                  # MGS_MESH_EVAL_NORMAL_DOUBLES: {pairs, sum |t|, t < 0, skipped} x 2
+MESH_SHADE_SHADED, MESH_SHADE_NORMAL, MESH_SHADE_COLOR, MESH_SHADE_MASK = 0, 1, 2, 3     # MGS_MESH_SHADE_*
+
+
+class MeshNormalsArgs(C.Structure):
+    _fields_ = ([("num_verts", C.c_int32), ("num_faces", C.c_int32)]
+                + [(n, _fp) for n in ("verts", "faces", "scratch", "normals", "record")])
+
+
+class MeshEvalNormalArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num", "num_ref", "num_faces", "num_ref_faces", "direction", "reserved0")]
+                + [(n, _fp) for n in ("d2", "index", "face", "ref_face", "normals", "ref_normals", "scratch", "record")])
+
+
+class MeshShadeArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "width", "height", "mode", "colors_u8")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "z_near")] + [("background", C.c_uint8 * 4)]
+                + [(n, _fp) for n in ("verts", "faces", "T", "face_id", "face_normal", "colors", "out")])
+
+
 _lib = None
 
 
@@ -681,6 +705,17 @@ def lib():
     L.mgs_vertex_visibility.argtypes = [C.POINTER(VertexVisibilityArgs), C.c_void_p]
     for fn in (L.mgs_mesh_cull_count, L.mgs_mesh_cull_emit):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshCullArgs), C.c_void_p]
+    for size_fn, cls, fns in ((L.mgs_mesh_normals_args_size, MeshNormalsArgs, (L.mgs_face_normals, L.mgs_vertex_normals)),
+                              (L.mgs_mesh_eval_normal_args_size, MeshEvalNormalArgs,
+                               (L.mgs_mesh_eval_normal_stats, L.mgs_mesh_eval_normal_finish)),
+                              (L.mgs_mesh_shade_args_size, MeshShadeArgs, (L.mgs_mesh_shade,))):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+        for fn in fns:
+            fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
+    L.mgs_vertex_normals_scratch_bytes.restype, L.mgs_vertex_normals_scratch_bytes.argtypes = C.c_uint64, [C.c_int32]
+    L.mgs_mesh_eval_normal_scratch_bytes.restype, L.mgs_mesh_eval_normal_scratch_bytes.argtypes = C.c_uint64, []
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

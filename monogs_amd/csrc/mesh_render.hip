@@ -9,6 +9,8 @@
 //                  striding the box.  The set-up is recomputed from the face index by the same function, the pixel by
 //                  the same shade(): both paths write the same keys
 //   k_mr_resolve   keys -> depth, face_id; record[2] = the length of the list
+//   k_mesh_shade   one lane per pixel: face_id -> uint8 rgb (headlight, normal, interpolated vertex colour, background mask);
+//                  the colour mode sets the face up again by the same setup_face and weighs by the same edge functions
 //   k_vis          one thread per vertex: seen_count[v] += the view sees it
 //   k_cull_init / k_cull_faces / k_cull_flags   the cull: face flags and vertex marks, their in-block ranks and block totals
 //   k_compact_scan / k_compact_emit             the stable compaction (compact_scan.h)
@@ -190,6 +192,63 @@ __global__ __launch_bounds__(kThreads) void k_mr_resolve(mgs_mesh_render_args A,
   if (i == 0) A.record[2] = min(*S.num_large, A.num_faces);
 }
 
+// ---- frames -----------------------------------------------------------------------------------------------------------
+// MGS_VIEW_RGB's quantisation (viewer.hip): fmaxf(NaN, 0) = 0, a NaN is black
+__device__ __forceinline__ unsigned char quantise(float x) { return (unsigned char)(int)mul_rn(fminf(fmaxf(x, 0.f), 1.f), 255.f); }
+
+// One lane per pixel: the colour of the face mgs_mesh_render left there (include/monogs_raster.h, mgs_mesh_shade).
+__global__ __launch_bounds__(kThreads) void k_mesh_shade(mgs_mesh_shade_args A, long long HW) {
+  const long long i = (long long)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= HW) return;
+  const int f = A.face_id[i];
+  unsigned char* o = A.out + 3 * (size_t)i;
+  bool hit = (unsigned)f < (unsigned)A.num_faces;
+  unsigned char rgb[3] = {A.background[0], A.background[1], A.background[2]};
+  if (A.mode == MGS_MESH_SHADE_MASK) {
+    if (hit) return;
+  } else if (hit && A.mode == MGS_MESH_SHADE_COLOR) {
+    mgs_mesh_render_args R{};
+    R.num_verts = A.num_verts; R.num_faces = A.num_faces; R.width = A.width; R.height = A.height;
+    R.verts = A.verts; R.faces = A.faces;
+    const Pinhole cam = pinhole_of(A.T, A.fx, A.fy, A.cx, A.cy, A.z_near);
+    FaceSetup P;
+    if (setup_face(R, cam, f, P) == kFaceDrawn) {
+      const long long X = 256ll * (i % A.width), Y = 256ll * (i / A.width);
+      double t[3];
+#pragma unroll
+      for (int k = 0; k < 3; k++) t[k] = mul_rn((double)weight(P, k, X, Y), P.iz[k]);
+      const double den = add_rn(add_rn(t[0], t[1]), t[2]);
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) {
+        double c[3];
+#pragma unroll
+        for (int k = 0; k < 3; k++) {
+          const size_t at = 3 * (size_t)A.faces[3 * (size_t)f + k] + ch;               // in [0,V): the face was set up
+          c[k] = A.colors_u8 ? (double)__fdiv_rn((float)static_cast<const unsigned char*>(A.colors)[at], 255.f)
+                             : (double)static_cast<const float*>(A.colors)[at];
+        }
+        const double num = add_rn(add_rn(mul_rn(t[0], c[0]), mul_rn(t[1], c[1])), mul_rn(t[2], c[2]));
+        rgb[ch] = quantise((float)div_rn(num, den));
+      }
+    }
+  } else if (hit) {
+    const float nx = A.face_normal[3 * (size_t)f], ny = A.face_normal[3 * (size_t)f + 1], nz = A.face_normal[3 * (size_t)f + 2];
+    float nc[3];
+#pragma unroll
+    for (int r = 0; r < 3; r++)
+      nc[r] = add_rn(add_rn(mul_rn(A.T[4 * r], nx), mul_rn(A.T[4 * r + 1], ny)), mul_rn(A.T[4 * r + 2], nz));
+    if (A.mode == MGS_MESH_SHADE_SHADED) {
+      rgb[0] = rgb[1] = rgb[2] = quantise(add_rn(0.25f, mul_rn(0.75f, fabsf(nc[2]))));
+    } else {
+      const float rx = __fdiv_rn(sub_rn((float)(i % A.width), A.cx), A.fx), ry = __fdiv_rn(sub_rn((float)(i / A.width), A.cy), A.fy);
+      const bool away = add_rn(add_rn(mul_rn(nc[0], rx), mul_rn(nc[1], ry)), nc[2]) > 0.f;
+#pragma unroll
+      for (int ch = 0; ch < 3; ch++) rgb[ch] = quantise(add_rn(mul_rn(0.5f, away ? -nc[ch] : nc[ch]), 0.5f));
+    }
+  }
+  o[0] = rgb[0]; o[1] = rgb[1]; o[2] = rgb[2];
+}
+
 // ---- visibility -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kThreads) void k_vis(mgs_vertex_visibility_args A) {
   const int i = blockIdx.x * kThreads + threadIdx.x;
@@ -275,6 +334,7 @@ extern "C" {
 int32_t mgs_mesh_render_args_size(void) { return (int32_t)sizeof(mgs_mesh_render_args); }
 int32_t mgs_vertex_visibility_args_size(void) { return (int32_t)sizeof(mgs_vertex_visibility_args); }
 int32_t mgs_mesh_cull_args_size(void) { return (int32_t)sizeof(mgs_mesh_cull_args); }
+int32_t mgs_mesh_shade_args_size(void) { return (int32_t)sizeof(mgs_mesh_shade_args); }
 
 uint64_t mgs_mesh_render_scratch_bytes(int32_t height, int32_t width, int32_t num_faces) {
   if (height < 1 || width < 1 || num_faces < 0 || num_faces > kMaxItems) return 0;
@@ -303,6 +363,22 @@ int32_t mgs_mesh_render(const mgs_mesh_render_args* a, void* stream) {
     launch("mr_large", mrender::k_mr_large, dim3(A.large_grid), th, st, A, S);
   }
   launch("mr_resolve", mrender::k_mr_resolve, dim3(grid_of(HW)), th, st, A, S, HW);
+  return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
+}
+
+int32_t mgs_mesh_shade(const mgs_mesh_shade_args* a, void* stream) {
+  if (!a || a->num_verts < 0 || a->num_faces < 0 || a->width < 1 || a->height < 1 || !a->face_id || !a->out)
+    return MGS_ERR_BAD_ARGUMENT;
+  if (a->mode < MGS_MESH_SHADE_SHADED || a->mode > MGS_MESH_SHADE_MASK) return MGS_ERR_BAD_ARGUMENT;
+  if (a->mode != MGS_MESH_SHADE_MASK && a->num_faces > 0) {
+    if (!a->T || !mrender::camera_ok(a->fx, a->fy, a->cx, a->cy, a->z_near)) return MGS_ERR_BAD_ARGUMENT;
+    if (a->mode == MGS_MESH_SHADE_COLOR ? (!a->faces || !a->colors || !a->verts || a->num_verts < 1) : !a->face_normal)
+      return MGS_ERR_BAD_ARGUMENT;
+  }
+  if (a->num_verts > kMaxItems || a->num_faces > kMaxItems) return MGS_ERR_UNSUPPORTED;
+  const long long HW = (long long)a->height * a->width;
+  if (3 * HW > mrender::kMaxPixels) return MGS_ERR_UNSUPPORTED;
+  launch("mesh_shade", mrender::k_mesh_shade, dim3(grid_of(HW)), dim3(mrender::kThreads), (hipStream_t)stream, *a, HW);
   return launches_ok() ? MGS_OK : MGS_ERR_LAUNCH;
 }
 

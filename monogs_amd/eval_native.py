@@ -282,7 +282,7 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
-              cull=None, **fuse_kw):
+              cull=None, normals: bool = False, preview=None, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -291,7 +291,11 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     None without a name.  With `gt` - a (verts, faces) mesh or a point tensor [M,3] on the device - the mesh is scored
     against it (mesh_eval.evaluate_mesh, which takes `eval_kw`), the scores are written as mesh_eval.json next to
     mesh.ply, and the dict of scores is returned instead of the path.  `cull` - evaluate_mesh's dict(views=..., ...) - culls
-    both meshes by visibility first; the scores then hold culled_pred_faces and culled_gt_faces."""
+    both meshes by visibility first; the scores then hold culled_pred_faces and culled_gt_faces.  eval_kw=dict(normals=True)
+    adds the normal-consistency numbers.  `normals=True` writes the vertex normals of the final mesh
+    (mesh_normals.vertex_normals, after `clean`) into mesh.ply.  `preview` - a view as mesh_render.view_tuple takes it -
+    writes the shaded frame of the mesh at that view (mesh_render.render_mesh_frame) as mesh_preview.png next to
+    mesh.ply (viewer.save_frame: a .ppm without PIL)."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -306,7 +310,15 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     verts, faces, colors = vol.extract_mesh(min_weight) if clean is None else vol.extract_mesh(min_weight, clean=clean)
     sub ="point_cloud/final" if final else "point_cloud/iteration_{}".format(str(iteration))
     path = os.path.join(name, sub, "mesh.ply")
-    write_mesh_ply(path, verts, faces, colors)
+    if normals:
+        from .mesh_normals import vertex_normals
+        write_mesh_ply(path, verts, faces, colors, normals=vertex_normals(verts, faces)[0])
+    else:
+        write_mesh_ply(path, verts, faces, colors)
+    if preview is not None:
+        from .mesh_render import render_mesh_frame
+        from .viewer import save_frame
+        save_frame(os.path.join(name, sub, "mesh_preview.png"), render_mesh_frame(verts, faces, preview))
     if gt is None:
         return path
     import json

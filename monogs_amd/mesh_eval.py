@@ -14,7 +14,9 @@ The mirrors ARE the contract:
     pair; the device gives the same bits;
   * `nearest_distance_torch` - chunked brute force in eager fp32 torch, one rounding per operation, the pair (d2, index)
     compared lexicographically; runs on CPU or GPU tensors; the device's grid search gives the same bits;
-  * `distance_stats_numpy`, `evaluate_mesh_numpy` - counts and maxima equal exactly, the fp64 sums to the order of adding.
+  * `distance_stats_numpy`, `evaluate_mesh_numpy` - counts and maxima equal exactly, the fp64 sums to the order of adding;
+  * `normal_stats_numpy` - with normals=True, n . m of the face normals (mesh_normals.py) of every sample and its nearest
+    neighbour in single fp32 roundings; pairs, flipped and skipped pairs exactly, the fp64 sum of |n . m| likewise.
 
 There is no CPU fall-back behind sample_surface / nearest_distance / evaluate_mesh: off the GPU they raise."""
 from __future__ import annotations
@@ -30,6 +32,7 @@ from ._device import device_rows, ptr as _ptr, stream_ptr, workspace
 
 METRIC_KEYS = ("accuracy", "completion", "chamfer", "precision", "recall", "completion_ratio", "f_score", "hausdorff",
                "n_pred", "n_gt", "bad_faces")
+NORMAL_KEYS = ("normal_accuracy", "normal_completion", "normal_consistency", "normal_flipped", "normal_skipped")
 SAMPLE_STREAM = 2          # Philox counter (j, 0, SAMPLE_STREAM, 0); keyframe seeding uses streams 0 and 1
 
 
@@ -175,6 +178,37 @@ def metrics_from_record(record, n_pred: int, n_gt: int) -> dict:
                 hausdorff=max(m0, m1), n_pred=int(n_pred), n_gt=int(n_gt), bad_faces=0)
 
 
+def normal_stats_numpy(face, d2, index, ref_face, normals, ref_normals) -> dict:
+    """{"n", "sum", "flipped", "skipped"} of one direction: for sample i on face `face[i]` with the neighbour index[i] on
+    face ref_face[index[i]], t = (n.x m.x + n.y m.y) + n.z m.z of the two face normals in single fp32 roundings; the
+    pair is skipped when an index is out of range, d2[i] is not finite or either normal is (0,0,0).  "sum" is the fp64
+    sum of |t|."""
+    face, index = np.asarray(face, np.int64).reshape(-1), np.asarray(index, np.int64).reshape(-1)
+    ref_face = np.asarray(ref_face, np.int64).reshape(-1)
+    d2 = np.asarray(d2, np.float32).reshape(-1)
+    nn, mm = np.asarray(normals, np.float32).reshape(-1, 3), np.asarray(ref_normals, np.float32).reshape(-1, 3)
+    ok = np.isfinite(d2) & (face >= 0) & (face < nn.shape[0]) & (index >= 0) & (index < ref_face.shape[0])
+    g = np.where(ok, ref_face[np.where(ok, index, 0)] if ref_face.size else 0, -1)
+    ok &= (g >= 0) & (g < mm.shape[0])
+    n, m = nn[face[ok]], mm[g[ok]]
+    both = (n != 0).any(axis=1) & (m != 0).any(axis=1)
+    n, m = n[both], m[both]
+    t = (n[:, 0] * m[:, 0] + n[:, 1] * m[:, 1]) + n[:, 2] * m[:, 2]
+    assert t.dtype == np.float32
+    return dict(n=int(t.size), sum=float(np.abs(t).astype(np.float64).sum()), flipped=int((t < 0).sum()),
+                skipped=int(d2.size - t.size))
+
+
+def normal_metrics_from_record(record) -> dict:
+    """The NORMAL_KEYS of evaluate_mesh(normals=True) from the eight doubles behind the record (include/monogs_raster.h:
+    {pairs, sum |t|, pairs with t < 0, skipped pairs} per direction)."""
+    n0, s0, f0, k0, n1, s1, f1, k1 = (float(x) for x in record)
+    nan = float("nan")
+    acc, comp = (s0 / n0 if n0 else nan), (s1 / n1 if n1 else nan)
+    return dict(normal_accuracy=acc, normal_completion=comp, normal_consistency=0.5 * (acc + comp),
+                normal_flipped=((f0 + f1) / (n0 + n1) if n0 + n1 else nan), normal_skipped=int(k0) + int(k1))
+
+
 def _matrix34(transform):
     """(s, R, t) or a 4x4 matrix -> twelve fp32 numbers, row-major [3,4]."""
     if isinstance(transform, (tuple, list)) and len(transform) == 3:
@@ -219,27 +253,44 @@ def _cull_arguments(cull, gt):
     return kw
 
 
+def _check_normals(normals, gt):
+    if normals and not _is_mesh(gt):
+        raise ValueError("evaluate_mesh: normals=True needs the ground truth as a (verts, faces) mesh")
+    return bool(normals)
+
+
 def evaluate_mesh_numpy(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, seed: int = 0, transform=None,
-                        with_record: bool = False, cull=None):
+                        with_record: bool = False, cull=None, normals: bool = False):
     """The mirror of evaluate_mesh on the host: the NumPy sampler, the brute-force distances (CPU torch), fp64 sums;
-    `cull` through the mirrors of mesh_render."""
+    `cull` through the mirrors of mesh_render, `normals` through face_normals_numpy and normal_stats_numpy."""
+    normals = _check_normals(normals, gt)
     pv = apply_transform(torch.as_tensor(np.asarray(pred[0], np.float32)).reshape(-1, 3), transform).numpy()
     culled = None
     if cull is not None:
         from .mesh_render import cull_pair
         pred, gt, *culled = cull_pair(True, (pv, pred[1]), gt, **_cull_arguments(cull, gt))
         pv = pred[0]
-    pp, _, prec = sample_surface_numpy(pv, pred[1], n_samples, seed, with_record=True)
+    pp, pf, prec = sample_surface_numpy(pv, pred[1], n_samples, seed, with_record=True)
     if _is_mesh(gt):
-        gp, _, grec = sample_surface_numpy(gt[0], gt[1], n_samples, seed + 1, with_record=True)
+        gp, gf, grec = sample_surface_numpy(gt[0], gt[1], n_samples, seed + 1, with_record=True)
     else:
-        gp, grec = np.ascontiguousarray(np.asarray(gt, np.float32)).reshape(-1, 3), np.zeros(4, np.int32)
-    record = np.zeros(_cabi.MESH_EVAL_RECORD_DOUBLES)
+        gp, gf, grec = np.ascontiguousarray(np.asarray(gt, np.float32)).reshape(-1, 3), None, np.zeros(4, np.int32)
+    N = _cabi.MESH_EVAL_RECORD_DOUBLES
+    record = np.zeros(N + (_cabi.MESH_EVAL_NORMAL_DOUBLES if normals else 0))
+    if normals:
+        from .mesh_normals import face_normals_numpy
+        pn, gn = face_normals_numpy(pv, pred[1])[0], face_normals_numpy(gt[0], gt[1])[0]
     for d, (a, b) in enumerate(((pp, gp), (gp, pp))):
-        st = distance_stats_numpy(nearest_distance_torch(torch.from_numpy(a), torch.from_numpy(b))[0].numpy(), threshold)
+        d2, index = (t.numpy() for t in nearest_distance_torch(torch.from_numpy(a), torch.from_numpy(b)))
+        st = distance_stats_numpy(d2, threshold)
         record[4 * d:4 * d + 4] = st["n"], st["below"], st["max"], st["sum"]
+        if normals:
+            st = normal_stats_numpy(*((pf, d2, index, gf, pn, gn) if d == 0 else (gf, d2, index, pf, gn, pn)))
+            record[N + 4 * d:N + 4 * d + 4] = st["n"], st["sum"], st["flipped"], st["skipped"]
     record[8:12] = prec[0], prec[1], grec[0], grec[1]
-    out = metrics_from_record(record, pp.shape[0], gp.shape[0])
+    out = metrics_from_record(record[:N], pp.shape[0], gp.shape[0])
+    if normals:
+        out.update(normal_metrics_from_record(record[N:]))
     if culled is not None:
         out["culled_pred_faces"], out["culled_gt_faces"] = culled
     return (out, record) if with_record else out
@@ -312,9 +363,10 @@ def nearest_distance(query, ref, cell_size=None):
     return d2, index
 
 
-def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_records=(None, None)) -> torch.Tensor:
+def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_records=(None, None),
+                   record=None) -> torch.Tensor:
     """The device record [12] f64 of the two directions (include/monogs_raster.h): one launch per direction and a final
-    one.  No host read."""
+    one.  No host read.  `record`: a float64 device tensor whose first twelve elements are written instead of a new one."""
     what = "distance_stats"
     if not torch.is_tensor(d2_pred_to_gt) or d2_pred_to_gt.device.type != "cuda":
         raise RuntimeError(f"{what} runs on the GPU only (HIP kernels, gfx950); distance_stats_numpy runs anywhere")
@@ -324,7 +376,8 @@ def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_record
         raise ValueError(f"{what}: threshold must be >= 0, got {threshold}")
     L = _cabi.lib()
     scratch = _workspace("stats", dev, (), L.mgs_mesh_eval_scratch_bytes, what)
-    record = torch.empty(_cabi.MESH_EVAL_RECORD_DOUBLES, dtype=torch.float64, device=dev)
+    if record is None:
+        record = torch.empty(_cabi.MESH_EVAL_RECORD_DOUBLES, dtype=torch.float64, device=dev)
     a = _cabi.MeshEvalArgs()
     a.threshold, a.scratch, a.record = thr, scratch.data_ptr(), record.data_ptr()
     keep = []
@@ -339,8 +392,28 @@ def distance_stats(d2_pred_to_gt, d2_gt_to_pred, threshold: float, sample_record
     return record
 
 
+def normal_stats(pred_side, gt_side, record: torch.Tensor) -> torch.Tensor:
+    """The eight doubles of the two directions of normal consistency (include/monogs_raster.h) into `record` [8] f64 on
+    the device.  A side is (face of every sample [n] i32, d2 [n], neighbour index [n] i32, face normals [F,3]) of one
+    mesh, all on the device of `record`.  One launch per direction and a final one.  No host read."""
+    dev = record.device
+    L = _cabi.lib()
+    scratch = _workspace("normal_stats", dev, (), L.mgs_mesh_eval_normal_scratch_bytes, "normal_stats")
+    a = _cabi.MeshEvalNormalArgs()
+    a.scratch, a.record = scratch.data_ptr(), record.data_ptr()
+    for d, (own, other) in enumerate(((pred_side, gt_side), (gt_side, pred_side))):
+        face, d2, index, normal = own
+        a.num, a.num_ref, a.num_faces, a.num_ref_faces = (int(t.shape[0]) for t in (face, other[0], normal, other[3]))
+        a.direction = d
+        a.d2, a.index, a.face, a.ref_face = _ptr(d2), _ptr(index), _ptr(face), _ptr(other[0])
+        a.normals, a.ref_normals = _ptr(normal), _ptr(other[3])
+        _cabi.check(L.mgs_mesh_eval_normal_stats(C.byref(a), stream_ptr(dev)), "mgs_mesh_eval_normal_stats")
+    _cabi.check(L.mgs_mesh_eval_normal_finish(C.byref(a), stream_ptr(dev)), "mgs_mesh_eval_normal_finish")
+    return record
+
+
 def evaluate_mesh(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, seed: int = 0, transform=None,
-                  with_record: bool = False, cull=None):
+                  with_record: bool = False, cull=None, normals: bool = False):
     """The geometry scores of the mesh `pred` = (verts, faces) against `gt` = (verts, faces), or a point tensor [M,3]
     that is used as it is: a dict of METRIC_KEYS, in the units of the input.  `transform` - (s, R, t) or a 4x4 matrix,
     e.g. the Sim(3) of the trajectory alignment - is applied to pred's vertices first (apply_transform).  pred is
@@ -351,8 +424,16 @@ def evaluate_mesh(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, s
     protocol of mesh_render first: after `transform`, in the ground truth's frame, both meshes lose what fewer than
     `min_views` of `views` (the ground-truth poses) saw - "gt" tests both against the ground-truth mesh's rendered depth,
     "self" each against its own, None the frustum alone - and what is left is scored.  The dict then also holds
-    culled_pred_faces and culled_gt_faces, and each of the two culls adds one host read (of its counts)."""
+    culled_pred_faces and culled_gt_faces, and each of the two culls adds one host read (of its counts).
+
+    `normals=True` (both sides must be meshes) adds NORMAL_KEYS behind METRIC_KEYS: with the unit normals of the two
+    meshes as they were sampled (mesh_normals.face_normals), every sample and its nearest neighbour give
+    t = n_sample . n_neighbour; normal_accuracy and normal_completion are the mean |t| of pred -> gt and gt -> pred,
+    normal_consistency their mean, normal_flipped the share of pairs with t < 0 (0 for two meshes wound alike, 1 when one
+    is wound the other way), normal_skipped the pairs without a neighbour or without a normal.  The eight doubles behind
+    them travel behind the record's twelve in the same single host read."""
     what = "evaluate_mesh"
+    normals = _check_normals(normals, gt)
     pv = _device_points(pred[0], what, "pred verts").detach().to(torch.float32)
     dev = pv.device
     pv = apply_transform(pv, transform)
@@ -362,16 +443,25 @@ def evaluate_mesh(pred, gt, n_samples: int = 200_000, threshold: float = 0.05, s
         kw = _cull_arguments(cull, gt)
         pred, gt, *culled = cull_pair(False, (pv, pred[1]), (_device_points(gt[0], what, "gt verts", dev), gt[1]), **kw)
         pv = pred[0]
-    pp, _, prec = sample_surface(pv, pred[1], n_samples, seed, with_record=True)
+    pp, pf, prec = sample_surface(pv, pred[1], n_samples, seed, with_record=True)
     if _is_mesh(gt):
-        gp, _, grec = sample_surface(_device_points(gt[0], what, "gt verts", dev), gt[1], n_samples, seed + 1,
-                                     with_record=True)
+        gv = _device_points(gt[0], what, "gt verts", dev)
+        gp, gf, grec = sample_surface(gv, gt[1], n_samples, seed + 1, with_record=True)
     else:
         gp, grec = _device_points(gt, what, "gt points", dev).detach().to(torch.float32).contiguous(), None
-    d_pg, _ = nearest_distance(pp, gp)
-    d_gp, _ = nearest_distance(gp, pp)
-    record = distance_stats(d_pg, d_gp, threshold, (prec, grec)).cpu().numpy()        # the one host read
-    out = metrics_from_record(record, pp.shape[0], gp.shape[0])
+    d_pg, i_pg = nearest_distance(pp, gp)
+    d_gp, i_gp = nearest_distance(gp, pp)
+    N = _cabi.MESH_EVAL_RECORD_DOUBLES
+    record = None
+    if normals:
+        from .mesh_normals import face_normals
+        record = torch.empty(N + _cabi.MESH_EVAL_NORMAL_DOUBLES, dtype=torch.float64, device=dev)
+        pn, gn = face_normals(pv, pred[1])[0], face_normals(gv, gt[1])[0]
+        normal_stats((pf, d_pg, i_pg, pn), (gf, d_gp, i_gp, gn), record[N:])
+    record = distance_stats(d_pg, d_gp, threshold, (prec, grec), record).cpu().numpy()        # the one host read
+    out = metrics_from_record(record[:N], pp.shape[0], gp.shape[0])
+    if normals:
+        out.update(normal_metrics_from_record(record[N:]))
     if culled is not None:
         out["culled_pred_faces"], out["culled_gt_faces"] = culled
     return (out, record) if with_record else out

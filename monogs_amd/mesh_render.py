@@ -429,3 +429,144 @@ def mesh_depth_l1(pred, gt, views, transform=None, z_near: float = 0.2):
 def mesh_depth_l1_numpy(pred, gt, views, transform=None, z_near: float = 0.2):
     """mesh_depth_l1 through the mirror render, on the host."""
     return _mesh_depth_l1(True, pred, gt, views, transform, z_near)
+
+
+# ---- frames ----------------------------------------------------------------------------------------------------------
+FRAME_MODES = ("shaded", "normal", "color", "depth")
+
+
+def _quantise(x):
+    """trunc(clamp(x, 0, 1) 255) in fp32, a NaN black: the viewer's rgb rule (viewer.compose_torch)."""
+    x = np.asarray(x, np.float32)
+    with np.errstate(all="ignore"):
+        x = np.clip(np.where(np.isnan(x), np.float32(0.0), x), np.float32(0.0), np.float32(1.0))
+        return (x * np.float32(255.0)).astype(np.uint8)
+
+
+def _frame_arguments(what, mode, colors, background, V):
+    if mode not in FRAME_MODES:
+        raise ValueError(f"{what}: mode must be one of {FRAME_MODES}, got {mode!r}")
+    if mode == "color":
+        if colors is None:
+            raise ValueError(f'{what}: mode "color" needs colors [V,3]')
+        if tuple(colors.shape) != (V, 3):
+            raise ValueError(f"{what}: colors must be [{V},3], got {tuple(colors.shape)}")
+    bg = _quantise(np.asarray(background, np.float32).reshape(-1))
+    if bg.shape != (3,):
+        raise ValueError(f"{what}: background is (r, g, b) in [0, 1]")
+    return bg
+
+
+def render_mesh_frame_numpy(verts, faces, view, mode: str = "shaded", colors=None, background=(0.0, 0.0, 0.0),
+                            z_near: float = 0.2):
+    """uint8 [H,W,3] in plain NumPy on top of render_mesh_depth_numpy: the contract of render_mesh_frame."""
+    from .mesh_normals import face_normals_numpy
+    what = "render_mesh_frame"
+    T, fx, fy, cx, cy, H, W = view_tuple(view)
+    v = np.ascontiguousarray(_as_numpy(verts, np.float32)).reshape(-1, 3)
+    f = _as_numpy(faces).reshape(-1, 3).astype(np.int64)
+    if colors is not None:
+        colors = _as_numpy(colors)
+    bg = _frame_arguments(what, mode, colors, background, v.shape[0])
+    depth, face_id, _ = render_mesh_depth_numpy(v, f, T, fx, fy, cx, cy, H, W, z_near)
+    hit = face_id >= 0
+    fid = np.where(hit, face_id, 0)
+    out = np.empty((H, W, 3), np.uint8)
+    out[:] = bg
+    if mode == "depth":
+        from .viewer import compose_torch
+        return np.where(hit[:, :, None], compose_torch(torch.from_numpy(depth), "depth").numpy(), out)
+    if not hit.any():
+        return out
+    T = _as_numpy(T).astype(np.float32).reshape(4, 4)
+    with np.errstate(all="ignore"):
+        if mode == "color":
+            col = colors.astype(np.float32) / np.float32(255.0) if colors.dtype == np.uint8 else colors.astype(np.float32)
+            u, w, zc = project_numpy(v, T, fx, fy, cx, cy)
+            X, Y = np.rint(u * np.float32(256.0)), np.rint(w * np.float32(256.0))
+            ys, xs = np.nonzero(hit)
+            tri = f[fid[ys, xs]]                                                  # [n,3]: drawn faces, so every vertex is good
+            x, y = X[tri].astype(np.int64), Y[tri].astype(np.int64)
+            iz = 1.0 / zc[tri].astype(np.float64)
+            a2 = (x[:, 1] - x[:, 0]) * (y[:, 2] - y[:, 0]) - (y[:, 1] - y[:, 0]) * (x[:, 2] - x[:, 0])
+            s = np.where(a2 > 0, 1, -1)
+            px, py = 256 * xs.astype(np.int64), 256 * ys.astype(np.int64)
+            edge = lambda a, b: s * ((x[:, b] - x[:, a]) * (py - y[:, a]) - (y[:, b] - y[:, a]) * (px - x[:, a]))
+            t = [edge(1, 2).astype(np.float64) * iz[:, 0], edge(2, 0).astype(np.float64) * iz[:, 1],
+                 edge(0, 1).astype(np.float64) * iz[:, 2]]
+            den = (t[0] + t[1]) + t[2]
+            c = col[tri].astype(np.float64)                                       # [n,3 corners,3 channels]
+            num = (t[0][:, None] * c[:, 0] + t[1][:, None] * c[:, 1]) + t[2][:, None] * c[:, 2]
+            out[ys, xs] = _quantise((num / den[:, None]).astype(np.float32))
+            return out
+        n = face_normals_numpy(v, f)[0][fid]                                      # [H,W,3]
+        nc = [(T[r, 0] * n[..., 0] + T[r, 1] * n[..., 1]) + T[r, 2] * n[..., 2] for r in range(3)]
+        if mode == "shaded":
+            grey = _quantise(np.float32(0.25) + np.float32(0.75) * np.abs(nc[2]))
+            rgb = np.stack([grey, grey, grey], -1)
+        else:
+            rx = ((np.arange(W, dtype=np.float32) - np.float32(cx)) / np.float32(fx))[None, :]
+            ry = ((np.arange(H, dtype=np.float32) - np.float32(cy)) / np.float32(fy))[:, None]
+            away = ((nc[0] * rx + nc[1] * ry) + nc[2]) > 0
+            rgb = np.stack([_quantise(np.float32(0.5) * np.where(away, -c, c) + np.float32(0.5)) for c in nc], -1)
+        assert nc[0].dtype == np.float32
+    return np.where(hit[:, :, None], rgb, out)
+
+
+def render_mesh_frame(verts, faces, view, mode: str = "shaded", colors=None, background=(0.0, 0.0, 0.0),
+                      z_near: float = 0.2):
+    """uint8 [H,W,3] on the device of `verts`: a picture of the mesh at `view` (what view_tuple accepts).
+    render_mesh_depth runs first, then face_normals where the mode needs them, then ONE launch, one lane per pixel; no
+    host read.  A pixel without a face gets `background` (r, g, b in [0, 1]); every channel is quantised as the viewer's
+    rgb frames are, trunc(clamp(x, 0, 1) 255).  With n_c the face's unit normal in the camera frame:
+
+      "shaded"  grey 0.25 + 0.75 |n_c.z|: a headlight, the same from both sides of a face;
+      "normal"  0.5 n_c + 0.5 as rgb, n_c turned to face the camera - surface.depth_normal_torch's orientation: its
+                normal is (d/dy) x (d/dx) of the back-projected depth, which always has n . ray < 0 - so n_c is negated
+                where n_c . ((x - cx) / fx, (y - cy) / fy, 1) > 0, and a wall seen head-on is (127, 127, 0) in both;
+      "color"   the vertex colours `colors` [V,3] (fp32 in [0, 1], or uint8), interpolated perspective-correctly with
+                the renderer's own edge functions and inverse depths;
+      "depth"   the viewer's depth view of the rendered depth (jet between 0.1 and the largest depth)."""
+    from .mesh_normals import face_normals
+    what = "render_mesh_frame"
+    T, fx, fy, cx, cy, H, W = view_tuple(view)
+    verts = _device_rows(verts, what, "verts", torch.float32)
+    dev = verts.device
+    faces = _device_rows(faces, what, "faces", torch.int32, dev)
+    V, F = int(verts.shape[0]), int(faces.shape[0])
+    if colors is not None:
+        if not torch.is_tensor(colors) or colors.device != dev:
+            raise ValueError(f"{what}: colors must be on the device of verts")
+        colors = colors.detach().contiguous() if colors.dtype == torch.uint8 else colors.detach().to(torch.float32).contiguous()
+    bg = _frame_arguments(what, mode, colors, background, V)
+    H, W = _check_image(what, H, W)
+    if 3 * H * W > _cabi.MESH_RENDER_MAX_PIXELS:
+        raise ValueError(f"{what}: {H} x {W} pixels: 3 H W must stay below 2^31")
+    depth, face_id, _ = render_mesh_depth(verts, faces, T, fx, fy, cx, cy, H, W, z_near)
+    T = _device_pose(T, what, dev)
+    L = _cabi.lib()
+    out = torch.empty(H, W, 3, dtype=torch.uint8, device=dev)
+    a = _cabi.MeshShadeArgs()
+    a.num_verts, a.num_faces, a.width, a.height = V, F, W, H
+    a.fx, a.fy, a.cx, a.cy, a.z_near = float(fx), float(fy), float(cx), float(cy), float(z_near)
+    a.background[0], a.background[1], a.background[2] = (int(b) for b in bg)
+    a.T, a.face_id, a.out = T.data_ptr(), face_id.data_ptr(), out.data_ptr()
+    keep = None
+    if mode == "depth":
+        from .viewer import _lut
+        lut = _lut(dev).contiguous()
+        keep = (lut, torch.empty(int(L.mgs_view_compose_scratch_bytes()), dtype=torch.uint8, device=dev))
+        c = _cabi.ViewComposeArgs()
+        c.width, c.height, c.mode = W, H, _cabi.VIEW_DEPTH
+        c.src, c.lut, c.out, c.scratch = depth.data_ptr(), lut.data_ptr(), out.data_ptr(), keep[1].data_ptr()
+        _cabi.check(L.mgs_view_compose(C.byref(c), stream_ptr(dev)), "mgs_view_compose")
+        a.mode = _cabi.MESH_SHADE_MASK
+    elif mode == "color":
+        a.mode, a.colors_u8 = _cabi.MESH_SHADE_COLOR, 1 if colors.dtype == torch.uint8 else 0
+        a.verts, a.faces, a.colors = _ptr(verts), _ptr(faces), _ptr(colors)
+    else:
+        keep = face_normals(verts, faces)[0]
+        a.mode = _cabi.MESH_SHADE_SHADED if mode == "shaded" else _cabi.MESH_SHADE_NORMAL
+        a.face_normal = _ptr(keep)
+    _cabi.check(L.mgs_mesh_shade(C.byref(a), stream_ptr(dev)), "mgs_mesh_shade")
+    return out

@@ -10,7 +10,8 @@ is coefficient j % (K - 1) of channel j // (K - 1).  Every value is the RAW para
 un-normalised quaternion).  An isotropic model has the single column scale_0.
 
 write_mesh_ply / read_mesh_ply hold the triangle mesh of monogs_amd.tsdf (DESIGN.md "Mesh export"): vertices
-x y z (fp32) red green blue (uchar), faces `property list uchar int vertex_indices`, binary little-endian.
+x y z (fp32), optionally nx ny nz (fp32), red green blue (uchar), faces `property list uchar int vertex_indices`, binary
+little-endian.
 
 Free functions on plain tensors, no GPU needed.  `plyfile` is not used: the writer emits the bytes above itself, so the
 agreement with a file plyfile would write is by the PLY specification, not by comparison."""
@@ -62,10 +63,15 @@ MESH_VERTEX_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("red", 
 MESH_FACE_DTYPE = np.dtype([("count", "u1"), ("vertex_indices", "<i4", (3,))])
 
 
-def mesh_ply_header(num_verts: int, num_faces: int) -> str:
+MESH_VERTEX_NORMAL_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("z", "<f4"), ("nx", "<f4"), ("ny", "<f4"), ("nz", "<f4"),
+                                     ("red", "u1"), ("green", "u1"), ("blue", "u1")])
+
+
+def mesh_ply_header(num_verts: int, num_faces: int, normals: bool = False) -> str:
     return ("ply\nformat binary_little_endian 1.0\n"
             f"element vertex {num_verts}\n"
             "property float x\nproperty float y\nproperty float z\n"
+            + ("property float nx\nproperty float ny\nproperty float nz\n" if normals else "") +
             "property uchar red\nproperty uchar green\nproperty uchar blue\n"
             f"element face {num_faces}\n"
             "property list uchar int vertex_indices\n"
@@ -79,10 +85,11 @@ def quantise_colors(colors) -> np.ndarray:
     return torch.floor(c * 255.0 + 0.5).to(torch.uint8).cpu().numpy()
 
 
-def write_mesh_ply(path: str, verts, faces, colors=None) -> None:
+def write_mesh_ply(path: str, verts, faces, colors=None, normals=None) -> None:
     """A triangle mesh as binary little-endian PLY: per vertex x y z (fp32) and red green blue (uint8; fp32 colours are
-    quantised by quantise_colors, None is white), per face a uchar count of 3 and three int32 vertex indices.  The
-    tensors are copied to the host once each."""
+    quantised by quantise_colors, None is white), per face a uchar count of 3 and three int32 vertex indices.  With
+    `normals` [V,3] the vertex element is x y z nx ny nz red green blue, the order MeshLab and Open3D write; without,
+    the file is what it was before there were normals.  The tensors are copied to the host once each."""
     v = torch.as_tensor(verts).detach().to(torch.float32).cpu().numpy().reshape(-1, 3)
     f = torch.as_tensor(faces).detach().to(torch.int32).cpu().numpy().reshape(-1, 3)
     if colors is None:
@@ -95,7 +102,12 @@ def write_mesh_ply(path: str, verts, faces, colors=None) -> None:
         raise ValueError(f"{c.shape[0]} colours for {v.shape[0]} vertices")
     if f.size and (f.min() < 0 or f.max() >= v.shape[0]):
         raise ValueError("face index out of range")
-    vr = np.empty(v.shape[0], MESH_VERTEX_DTYPE)
+    vr = np.empty(v.shape[0], MESH_VERTEX_DTYPE if normals is None else MESH_VERTEX_NORMAL_DTYPE)
+    if normals is not None:
+        n = torch.as_tensor(normals).detach().to(torch.float32).cpu().numpy().reshape(-1, 3)
+        if n.shape[0] != v.shape[0]:
+            raise ValueError(f"{n.shape[0]} normals for {v.shape[0]} vertices")
+        vr["nx"], vr["ny"], vr["nz"] = n[:, 0], n[:, 1], n[:, 2]
     vr["x"], vr["y"], vr["z"] = v[:, 0], v[:, 1], v[:, 2]
     vr["red"], vr["green"], vr["blue"] = c[:, 0], c[:, 1], c[:, 2]
     fr = np.empty(f.shape[0], MESH_FACE_DTYPE)
@@ -105,14 +117,15 @@ def write_mesh_ply(path: str, verts, faces, colors=None) -> None:
     if d:
         os.makedirs(d, exist_ok=True)
     with open(path, "wb") as fh:
-        fh.write(mesh_ply_header(v.shape[0], f.shape[0]).encode("ascii"))
+        fh.write(mesh_ply_header(v.shape[0], f.shape[0], normals is not None).encode("ascii"))
         fh.write(vr.tobytes())
         fh.write(fr.tobytes())
 
 
-def read_mesh_ply(path: str):
-    """The inverse of write_mesh_ply: (verts [V,3] f32, faces [F,3] i32, colors [V,3] uint8) as CPU tensors.  Only the
-    layout write_mesh_ply emits is read."""
+def read_mesh_ply(path: str, with_normals: bool = False):
+    """The inverse of write_mesh_ply: (verts [V,3] f32, faces [F,3] i32, colors [V,3] uint8) as CPU tensors, of a file
+    with or without normals; `with_normals` adds a fourth element, normals [V,3] f32 or None when the file has none.
+    Only the two layouts write_mesh_ply emits are read."""
     with open(path, "rb") as fh:
         blob = fh.read()
     end = blob.find(b"end_header\n")
@@ -124,19 +137,27 @@ def read_mesh_ply(path: str):
     if "vertex" not in counts or "face" not in counts:
         raise ValueError(f"{path}: a vertex and a face element are expected")
     nv, nf = counts["vertex"], counts["face"]
-    if blob[:body].decode("ascii") != mesh_ply_header(nv, nf):
+    header = blob[:body].decode("ascii")
+    has_normals = header == mesh_ply_header(nv, nf, True)
+    if not has_normals and header != mesh_ply_header(nv, nf):
         raise ValueError(f"{path}: not the layout write_mesh_ply emits")
-    need = nv * MESH_VERTEX_DTYPE.itemsize + nf * MESH_FACE_DTYPE.itemsize
+    vertex_dtype = MESH_VERTEX_NORMAL_DTYPE if has_normals else MESH_VERTEX_DTYPE
+    need = nv * vertex_dtype.itemsize + nf * MESH_FACE_DTYPE.itemsize
     if len(blob) - body < need:
         raise ValueError(f"{path}: {need} bytes of data expected, file too short")
-    vr = np.frombuffer(blob, MESH_VERTEX_DTYPE, count=nv, offset=body)
-    fr = np.frombuffer(blob, MESH_FACE_DTYPE, count=nf, offset=body + nv * MESH_VERTEX_DTYPE.itemsize)
+    vr = np.frombuffer(blob, vertex_dtype, count=nv, offset=body)
+    fr = np.frombuffer(blob, MESH_FACE_DTYPE, count=nf, offset=body + nv * vertex_dtype.itemsize)
     if nf and (fr["count"] != 3).any():
         raise ValueError(f"{path}: only triangles are read")
     verts = np.stack([vr["x"], vr["y"], vr["z"]], 1).astype(np.float32)
     cols = np.stack([vr["red"], vr["green"], vr["blue"]], 1).astype(np.uint8)
-    return (torch.from_numpy(verts.reshape(nv, 3)), torch.from_numpy(fr["vertex_indices"].astype(np.int32).reshape(nf, 3)),
-            torch.from_numpy(cols.reshape(nv, 3)))
+    out = (torch.from_numpy(verts.reshape(nv, 3)), torch.from_numpy(fr["vertex_indices"].astype(np.int32).reshape(nf, 3)),
+           torch.from_numpy(cols.reshape(nv, 3)))
+    if not with_normals:
+        return out
+    if not has_normals:
+        return out + (None,)
+    return out + (torch.from_numpy(np.stack([vr["nx"], vr["ny"], vr["nz"]], 1).astype(np.float32).reshape(nv, 3)),)
 
 
 def read_gaussian_ply(path: str) -> Dict[str, torch.Tensor]:

@@ -507,7 +507,7 @@ def evaluate_mesh(result, gt, voxel_size: float, monocular: bool = True, mesh_kw
     Chamfer) against `gt` - a (verts, faces) mesh or a point tensor [M,3] on the device, in the ground truth's frame.  The
     surface is reconstruct_mesh(result, voxel_size, **mesh_kw); it is brought into the ground truth's frame by the
     alignment `evaluate` uses for the ATE over all tracked frames - Sim(3) when `monocular`, SE(3) otherwise - and scored
-    with `kw` (n_samples, threshold, seed).  `cull` - True, or a dict of mesh_eval.evaluate_mesh's cull keys (occlusion,
+    with `kw` (n_samples, threshold, seed; normals=True adds the normal-consistency numbers).  `cull` - True, or a dict of mesh_eval.evaluate_mesh's cull keys (occlusion,
     eps, min_views, rule) - applies the visibility protocol first, with the views built from the cameras' ground-truth
     poses T_gt, their intrinsics and their image size (a dict may bring its own `views`)."""
     import numpy as np
