@@ -1879,6 +1879,59 @@ int32_t mgs_mesh_eval_normal_finish(const mgs_mesh_eval_normal_args* args, void*
 int32_t mgs_mesh_shade_args_size(void);
 int32_t mgs_mesh_shade(const mgs_mesh_shade_args* args, void* stream);
 
+/* ---- mesh simplification ("Mesh simplification") -------------------------------------------------------
+ * Vertex clustering of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL): the
+ * vertices of one cell of a uniform grid become one vertex, faces that collapse or repeat are dropped.  The NumPy mirror
+ * mesh_simplify.simplify_mesh_numpy is the contract; the device equals it bit for bit, and two calls give the same bytes.
+ *   Origin       `origin`, or with origin_from_verts = 1 the per-axis minimum over the vertices whose three coordinates
+ *                are finite (an integer minimum over order-preserving keys of the floats; no host read).
+ *   Cell         per axis, one fp32 rounding each: t = (v - o) / cell (IEEE division), c = floor(t), fr = t - c.  fr lies
+ *                in [0, 1]: the difference is exact except for a negative t so small that it rounds to 1.  c must lie in
+ *                [-2^20, 2^20); the key packs the three c + 2^20 into 63 bits.  A vertex with a non-finite coordinate or a
+ *                cell out of range is BAD: it joins no cluster and is counted into counts[5].
+ *   Clusters     the vertices of one key; the label of a cluster is its smallest vertex index.
+ *   Position     per axis q = trunc(fr 2^24) as int64, S = sum of q over the n vertices of the cluster (< 2^55),
+ *                m = double(S) / (double(n) 2^24), position = float(double(o) + (double(c) + m) double(cell)), every fp64
+ *                operation one rounding, no contraction.
+ *   Colour       x = fminf(fmaxf(x, 0), 1) (NaN gives 0), q = trunc(x 2^24), mean = float(double(S) / (double(n) 2^24)).
+ *   Faces        every index is mapped to its label.  A face with two equal labels is COLLAPSED and dropped.  Two
+ *                surviving faces whose label triples are equal as sets (any order, either winding) are DUPLICATES: the
+ *                one with the smallest face index stays.  Kept faces keep their relative order and their winding.  A
+ *                face with an index outside [0,V) is BAD: never emitted, counted into counts[6].
+ *   Output       a cluster is emitted iff a kept face names it, in ascending label order; the faces are re-indexed.
+ *   mgs_mesh_simplify_count  keys, both hash sets, sums, flags and scan into `scratch`; counts = (V', F', clusters,
+ *                            collapsed faces, duplicate faces, bad vertices, bad faces, spare) on the device
+ *   mgs_mesh_simplify_emit   after the caller has read counts: writes out_num_verts vertices / colours and out_num_faces
+ *                            faces (never more: the counts bound every store).  Both 0 launches nothing.
+ * `scratch` (mgs_mesh_simplify_scratch_bytes; no initial state) carries sums and flags from count to emit; `verts`,
+ * `faces`, `cell` and the origin must not change in between.  A null struct, scratch, counts (count), a needed array that
+ * is null, a negative size, a cell that is not a finite value > 0, a non-finite given origin: MGS_ERR_BAD_ARGUMENT.
+ * 3 V >= 2^31 or 3 F >= 2^31: MGS_ERR_UNSUPPORTED, and scratch_bytes is 0.  V = 0 or F = 0 is legal.  A refused call
+ * launches nothing and writes nothing. */
+#define MGS_MESH_SIMPLIFY_COUNTS 8
+
+typedef struct mgs_mesh_simplify_args {
+  int32_t num_verts, num_faces;
+  float cell;                /* edge of a cell, finite and > 0 */
+  int32_t origin_from_verts; /* 1: the per-axis minimum of the finite vertices instead of `origin` */
+  float origin[3];
+  int32_t reserved0;
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3] */
+  const float* colors;       /* [V,3] or NULL (then `out_colors` is not written) */
+  void* scratch;
+  int32_t* counts;           /* [MGS_MESH_SIMPLIFY_COUNTS] device (count only) */
+  float* out_verts;          /* [out_num_verts,3] (emit only) */
+  int32_t* out_faces;        /* [out_num_faces,3] (emit only) */
+  float* out_colors;         /* [out_num_verts,3] (emit only, with `colors`) */
+  int32_t out_num_verts, out_num_faces;   /* as read from counts[0], counts[1] (emit only) */
+} mgs_mesh_simplify_args;
+
+int32_t mgs_mesh_simplify_args_size(void);
+uint64_t mgs_mesh_simplify_scratch_bytes(int32_t num_verts, int32_t num_faces);
+int32_t mgs_mesh_simplify_count(const mgs_mesh_simplify_args* args, void* stream);
+int32_t mgs_mesh_simplify_emit(const mgs_mesh_simplify_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

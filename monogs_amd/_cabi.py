@@ -55,6 +55,7 @@ EXPORTS = (
     "mgs_mesh_normals_args_size", "mgs_vertex_normals_scratch_bytes", "mgs_face_normals", "mgs_vertex_normals",
     "mgs_mesh_eval_normal_args_size", "mgs_mesh_eval_normal_scratch_bytes", "mgs_mesh_eval_normal_stats",
     "mgs_mesh_eval_normal_finish", "mgs_mesh_shade_args_size", "mgs_mesh_shade",
+    "mgs_mesh_simplify_args_size", "mgs_mesh_simplify_scratch_bytes", "mgs_mesh_simplify_count", "mgs_mesh_simplify_emit",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -475,6 +476,16 @@ class MeshShadeArgs(C.Structure):
                 + [(n, _fp) for n in ("verts", "faces", "T", "face_id", "face_normal", "colors", "out")])
 
 
+MESH_SIMPLIFY_COUNTS = 8                      # MGS_MESH_SIMPLIFY_COUNTS: V', F', clusters, collapsed, duplicates, bad vertices, bad faces, spare
+
+
+class MeshSimplifyArgs(C.Structure):
+    _fields_ = ([("num_verts", C.c_int32), ("num_faces", C.c_int32), ("cell", C.c_float), ("origin_from_verts", C.c_int32),
+                 ("origin", C.c_float * 3), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("verts", "faces", "colors", "scratch", "counts", "out_verts", "out_faces", "out_colors")]
+                + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
+
+
 _lib = None
 
 
@@ -716,6 +727,13 @@ def lib():
             fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
     L.mgs_vertex_normals_scratch_bytes.restype, L.mgs_vertex_normals_scratch_bytes.argtypes = C.c_uint64, [C.c_int32]
     L.mgs_mesh_eval_normal_scratch_bytes.restype, L.mgs_mesh_eval_normal_scratch_bytes.argtypes = C.c_uint64, []
+    L.mgs_mesh_simplify_args_size.restype, L.mgs_mesh_simplify_args_size.argtypes = C.c_int32, []
+    if L.mgs_mesh_simplify_args_size() != C.sizeof(MeshSimplifyArgs):
+        raise NativeLibraryError("MeshSimplifyArgs does not have the size of mgs_mesh_simplify_args")
+    L.mgs_mesh_simplify_scratch_bytes.restype = C.c_uint64
+    L.mgs_mesh_simplify_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
+    for fn in (L.mgs_mesh_simplify_count, L.mgs_mesh_simplify_emit):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshSimplifyArgs), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

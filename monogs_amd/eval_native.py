@@ -282,7 +282,7 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
-              cull=None, normals: bool = False, preview=None, **fuse_kw):
+              cull=None, normals: bool = False, preview=None, simplify=None, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -295,7 +295,9 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     adds the normal-consistency numbers.  `normals=True` writes the vertex normals of the final mesh
     (mesh_normals.vertex_normals, after `clean`) into mesh.ply.  `preview` - a view as mesh_render.view_tuple takes it -
     writes the shaded frame of the mesh at that view (mesh_render.render_mesh_frame) as mesh_preview.png next to
-    mesh.ply (viewer.save_frame: a .ppm without PIL)."""
+    mesh.ply (viewer.save_frame: a .ppm without PIL).  `simplify` - a dict of mesh_simplify.simplify_mesh keyword
+    arguments, e.g. dict(factor=2) for cells of two voxels (TSDFVolume.extract_mesh) - merges the vertices of every cell
+    after `clean` and before the normals, the preview and the scores, so that all three describe the file written."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -307,7 +309,10 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         if background is None:
             background = torch.zeros(3, device=vol.get_xyz.device)
         vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
-    verts, faces, colors = vol.extract_mesh(min_weight) if clean is None else vol.extract_mesh(min_weight, clean=clean)
+    if simplify is not None:
+        verts, faces, colors = vol.extract_mesh(min_weight, clean=clean, simplify=simplify)
+    else:
+        verts, faces, colors = vol.extract_mesh(min_weight) if clean is None else vol.extract_mesh(min_weight, clean=clean)
     sub ="point_cloud/final" if final else "point_cloud/iteration_{}".format(str(iteration))
     path = os.path.join(name, sub, "mesh.ply")
     if normals:
