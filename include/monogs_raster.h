@@ -1932,6 +1932,74 @@ uint64_t mgs_mesh_simplify_scratch_bytes(int32_t num_verts, int32_t num_faces);
 int32_t mgs_mesh_simplify_count(const mgs_mesh_simplify_args* args, void* stream);
 int32_t mgs_mesh_simplify_emit(const mgs_mesh_simplify_args* args, void* stream);
 
+/* ---- mesh edges, topology and smoothing ("Mesh edges and smoothing") ------------------------------------
+ * The unique undirected edges of an indexed triangle mesh (faces [F,3] i32 over V vertices) with the number of faces on
+ * each, and smoothing over the unique-edge neighbours.  The NumPy mirrors mesh_topology.mesh_edges_numpy and
+ * mesh_smooth.smooth_mesh_numpy are the contract; the device equals them bit for bit, and two calls give the same bytes.
+ *   Half-edges   half-edge 3 f + k runs from faces[f,k] to faces[f,(k+1)%3]; its key is (lo << 32) | hi of the two.
+ *   Faces        a face with an index outside [0,V) is BAD: no edge, counted into record[9].  A face with two equal
+ *                indices is DEGENERATE: no edge, counted into record[8].
+ *   Edges        the representative of an edge is the smallest half-edge index with its key; edges are emitted in
+ *                ascending representative order as (lo, hi), edge_faces is the number of half-edges with the key.
+ *   Vertices     vertex_degree: unique edges at the vertex.  vertex_flags bit 0: referenced (degree > 0), bit 1: on an
+ *                edge whose count is not 2.
+ *   record       [0] edges, [1] sum of the degrees (2 edges), [2] referenced vertices, [3] vertices with flag bit 1,
+ *                [4] edges of count 1, [5] of count 2, [6] of count >= 3, [7] of count 2 with both half-edges in one
+ *                direction, [8] degenerate faces, [9] bad faces, [10] bad vertices (mgs_mesh_smooth), the rest 0.
+ *   mgs_mesh_edges_count  the edge set, the class counters, vertex_degree and vertex_flags; the record on the device
+ *   mgs_mesh_edges_emit   after the caller has read record[0]: writes out_num_edges edges and counts (never more: the
+ *                         count bounds every store).  0 launches nothing.
+ *   mgs_mesh_smooth       `iterations` times a step of weight lam and, with taubin = 1, a step of weight mu; out_verts
+ *                         [V,3].  One step, Jacobi style, with E = (bits >> 23) - 127 of the largest |coordinate| of
+ *                         the input and K = 28: a vertex of degree 0, and with boundary_free = 0 a vertex whose flag
+ *                         bit 1 is set, keeps its bits; every other one, per axis, S = sum over its d neighbours of
+ *                         q(p_u) as int64, q(p) = int64(fmax(fmin(ldexp(double(p), K - E), 2^62), -2^62)),
+ *                         m = ldexp(double(S) / double(d), E - K), p' = float(double(p) + w (m - double(p))), every
+ *                         fp64 operation one rounding, no contraction.  A vertex with a non-finite coordinate is BAD:
+ *                         counted into record[10]; the output then means nothing.
+ * `scratch` (mgs_mesh_edges_scratch_bytes / mgs_mesh_smooth_scratch_bytes; no initial state) carries the set from count
+ * to emit; `faces` must not change in between.  A null struct, scratch, record, a needed array that is null, a negative
+ * size, iterations outside [0, MGS_MESH_SMOOTH_MAX_ITERATIONS], lam outside (0, 1], with taubin a mu outside [-1, 0):
+ * MGS_ERR_BAD_ARGUMENT.  3 V >= 2^31 or 3 F > 2^30 (the hash table holds at most 2^31 words): MGS_ERR_UNSUPPORTED, and
+ * scratch_bytes is 0.  V = 0 or F = 0 is legal.  A refused call launches nothing and writes nothing. */
+#define MGS_MESH_EDGES_RECORD_INTS 16
+#define MGS_MESH_SMOOTH_MAX_ITERATIONS 1000
+
+typedef struct mgs_mesh_edges_args {
+  int32_t num_verts, num_faces;
+  const int32_t* faces;      /* [F,3] */
+  void* scratch;
+  int32_t* record;           /* [MGS_MESH_EDGES_RECORD_INTS] device */
+  int32_t* vertex_degree;    /* [V] (count only) */
+  int32_t* vertex_flags;     /* [V] (count only) */
+  int32_t* edges;            /* [out_num_edges,2] (emit only) */
+  int32_t* edge_faces;       /* [out_num_edges] (emit only) */
+  int32_t out_num_edges;     /* as read from record[0] (emit only) */
+  int32_t reserved0;
+} mgs_mesh_edges_args;
+
+typedef struct mgs_mesh_smooth_args {
+  int32_t num_verts, num_faces;
+  int32_t iterations;        /* in [0, MGS_MESH_SMOOTH_MAX_ITERATIONS] */
+  int32_t taubin;            /* 1: every iteration is a lam step and a mu step; 0: a lam step */
+  int32_t boundary_free;     /* 0: vertices with flag bit 1 are pinned; 1: they move */
+  float lam, mu;
+  int32_t reserved0;
+  const float* verts;        /* [V,3] */
+  const int32_t* faces;      /* [F,3] */
+  void* scratch;
+  int32_t* record;           /* [MGS_MESH_EDGES_RECORD_INTS] device */
+  float* out_verts;          /* [V,3], not `verts` */
+} mgs_mesh_smooth_args;
+
+int32_t mgs_mesh_edges_args_size(void);
+uint64_t mgs_mesh_edges_scratch_bytes(int32_t num_verts, int32_t num_faces);
+int32_t mgs_mesh_edges_count(const mgs_mesh_edges_args* args, void* stream);
+int32_t mgs_mesh_edges_emit(const mgs_mesh_edges_args* args, void* stream);
+int32_t mgs_mesh_smooth_args_size(void);
+uint64_t mgs_mesh_smooth_scratch_bytes(int32_t num_verts, int32_t num_faces);
+int32_t mgs_mesh_smooth(const mgs_mesh_smooth_args* args, void* stream);
+
 /* Per-kernel timing (diagnostics; used by bench.py for the roofline line).  While
  * enabled every kernel launch is bracketed by hipEvents on the launch stream.
  * mgs_profile_read waits for the recorded events, aggregates them by kernel name into

@@ -56,6 +56,8 @@ EXPORTS = (
     "mgs_mesh_eval_normal_args_size", "mgs_mesh_eval_normal_scratch_bytes", "mgs_mesh_eval_normal_stats",
     "mgs_mesh_eval_normal_finish", "mgs_mesh_shade_args_size", "mgs_mesh_shade",
     "mgs_mesh_simplify_args_size", "mgs_mesh_simplify_scratch_bytes", "mgs_mesh_simplify_count", "mgs_mesh_simplify_emit",
+    "mgs_mesh_edges_args_size", "mgs_mesh_edges_scratch_bytes", "mgs_mesh_edges_count", "mgs_mesh_edges_emit",
+    "mgs_mesh_smooth_args_size", "mgs_mesh_smooth_scratch_bytes", "mgs_mesh_smooth",
 )
 
 _fp = C.c_void_p  # device pointers travel as plain addresses
@@ -486,6 +488,25 @@ class MeshSimplifyArgs(C.Structure):
                 + [("out_num_verts", C.c_int32), ("out_num_faces", C.c_int32)])
 
 
+MESH_EDGES_RECORD_INTS = 16                   # MGS_MESH_EDGES_RECORD_INTS: edges, degree sum, referenced, boundary vertices,
+                                              # boundary / manifold / non-manifold / inconsistent edges, degenerate faces,
+                                              # bad faces, bad vertices, spare
+MESH_SMOOTH_MAX_ITERATIONS = 1000             # MGS_MESH_SMOOTH_MAX_ITERATIONS
+MESH_EDGES_MAX_FACES = (1 << 30) // 3         # 3 F <= 2^30: the hash table of the half-edges holds at most 2^31 words
+
+
+class MeshEdgesArgs(C.Structure):
+    _fields_ = ([("num_verts", C.c_int32), ("num_faces", C.c_int32)]
+                + [(n, _fp) for n in ("faces", "scratch", "record", "vertex_degree", "vertex_flags", "edges", "edge_faces")]
+                + [("out_num_edges", C.c_int32), ("reserved0", C.c_int32)])
+
+
+class MeshSmoothArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("num_verts", "num_faces", "iterations", "taubin", "boundary_free")]
+                + [("lam", C.c_float), ("mu", C.c_float), ("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("verts", "faces", "scratch", "record", "out_verts")])
+
+
 _lib = None
 
 
@@ -734,6 +755,16 @@ def lib():
     L.mgs_mesh_simplify_scratch_bytes.argtypes = [C.c_int32, C.c_int32]
     for fn in (L.mgs_mesh_simplify_count, L.mgs_mesh_simplify_emit):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(MeshSimplifyArgs), C.c_void_p]
+    for size_fn, cls, bytes_fn, fns in (
+            (L.mgs_mesh_edges_args_size, MeshEdgesArgs, L.mgs_mesh_edges_scratch_bytes,
+             (L.mgs_mesh_edges_count, L.mgs_mesh_edges_emit)),
+            (L.mgs_mesh_smooth_args_size, MeshSmoothArgs, L.mgs_mesh_smooth_scratch_bytes, (L.mgs_mesh_smooth,))):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+        bytes_fn.restype, bytes_fn.argtypes = C.c_uint64, [C.c_int32, C.c_int32]
+        for fn in fns:
+            fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
     if L.mgs_abi_version() != ABI_VERSION:
         raise NativeLibraryError(
             f"ABI mismatch: library {L.mgs_abi_version()} vs binding {ABI_VERSION}")

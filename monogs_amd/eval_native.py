@@ -282,7 +282,7 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
-              cull=None, normals: bool = False, preview=None, simplify=None, **fuse_kw):
+              cull=None, normals: bool = False, preview=None, simplify=None, smooth=None, topology: bool = False, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -297,7 +297,10 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     writes the shaded frame of the mesh at that view (mesh_render.render_mesh_frame) as mesh_preview.png next to
     mesh.ply (viewer.save_frame: a .ppm without PIL).  `simplify` - a dict of mesh_simplify.simplify_mesh keyword
     arguments, e.g. dict(factor=2) for cells of two voxels (TSDFVolume.extract_mesh) - merges the vertices of every cell
-    after `clean` and before the normals, the preview and the scores, so that all three describe the file written."""
+    after `clean` and before the normals, the preview and the scores, so that all three describe the file written.
+    `smooth` - a dict of mesh_smooth.smooth_mesh keyword arguments, e.g. dict(iterations=10) - moves the vertices after
+    `clean` and before `simplify`.  `topology=True` writes mesh_topology.json next to mesh.ply: the dict of
+    mesh_topology.mesh_topology(faces, V, components=True) for the mesh as written."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -309,7 +312,9 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         if background is None:
             background = torch.zeros(3, device=vol.get_xyz.device)
         vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
-    if simplify is not None:
+    if smooth is not None:
+        verts, faces, colors = vol.extract_mesh(min_weight, clean=clean, simplify=simplify, smooth=smooth)
+    elif simplify is not None:
         verts, faces, colors = vol.extract_mesh(min_weight, clean=clean, simplify=simplify)
     else:
         verts, faces, colors = vol.extract_mesh(min_weight) if clean is None else vol.extract_mesh(min_weight, clean=clean)
@@ -324,6 +329,11 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         from .mesh_render import render_mesh_frame
         from .viewer import save_frame
         save_frame(os.path.join(name, sub, "mesh_preview.png"), render_mesh_frame(verts, faces, preview))
+    if topology:
+        import json
+        from .mesh_topology import mesh_topology
+        with open(os.path.join(name, sub, "mesh_topology.json"), "w", encoding="utf-8") as fh:
+            json.dump(mesh_topology(faces, int(verts.shape[0]), components=True), fh, indent=4)
     if gt is None:
         return path
     import json

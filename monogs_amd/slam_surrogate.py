@@ -474,7 +474,7 @@ def evaluate(result, frames, dev, every: int = 1, monocular: bool = True, native
 
 
 def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_depth=None, margin: float = 0.1,
-                     min_weight: float = 1.0, clean=None, simplify=None, **fuse_kw):
+                     min_weight: float = 1.0, clean=None, simplify=None, smooth=None, **fuse_kw):
     """The surface of a finished run: fuses every `every_keyframe`-th keyframe of a run_sequence `result` (its
     "cameras", "kf_ids", "gaussians") into a tsdf.TSDFVolume sized from the map and extracts the mesh:
     (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device.  By default each keyframe contributes the map's
@@ -483,7 +483,9 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
     to tsdf.fuse_map: depth_mode="median" fuses the median depth of every rendered view instead of depth / opacity.
     `clean` - a dict of mesh_clean.clean_mesh keyword arguments, e.g. dict(keep_largest=1) - drops the floaters.
     `simplify` - a dict of mesh_simplify.simplify_mesh keyword arguments, e.g. dict(factor=2) for cells of two voxels -
-    merges the vertices of every cell afterwards (TSDFVolume.extract_mesh)."""
+    merges the vertices of every cell afterwards (TSDFVolume.extract_mesh).  `smooth` - a dict of
+    mesh_smooth.smooth_mesh keyword arguments, e.g. dict(iterations=10) - moves the vertices after `clean` and before
+    `simplify`."""
     from . import tsdf
     gm = result["gaussians"]
     ids = list(result["kf_ids"])[::max(1, int(every_keyframe))]
@@ -499,6 +501,8 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
             img = img if torch.is_tensor(img) and img.dtype == torch.float32 and img.dim() == 3 else None
             vol.integrate(sensor_depth[k], cam.T, cam.fx, cam.fy, cam.cx, cam.cy, image=img,
                           depth_max=fuse_kw.get("depth_max", math.inf))
+    if smooth is not None:
+        return vol.extract_mesh(min_weight, clean=clean, simplify=simplify, smooth=smooth)
     if simplify is not None:
         return vol.extract_mesh(min_weight, clean=clean, simplify=simplify)
     if clean is None:

@@ -366,14 +366,16 @@ class TSDFVolume:
         a.scratch, a.counts = self._scratch.data_ptr(), self._counts.data_ptr()
         return a
 
-    def extract_mesh(self, min_weight: float = 1.0, clean=None, simplify=None):
+    def extract_mesh(self, min_weight: float = 1.0, clean=None, simplify=None, smooth=None):
         """(verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device; empty tensors when nothing crosses.
         One host read, of (V, F), between the scan and the emission.  `clean` - a dict of mesh_clean.clean_mesh keyword
         arguments, e.g. dict(keep_largest=1) or dict(min_faces=50) - drops the floaters from the extracted mesh (one
         more host read); None leaves it as extracted.  `simplify` - a dict of mesh_simplify.simplify_mesh keyword
         arguments, applied after `clean` (one more host read) - merges the vertices of every cell of edge `cell`, or of
         `factor` voxels (dict(factor=2); not both), counted from `origin`, which defaults to the volume's; None leaves
-        the mesh as it is."""
+        the mesh as it is.  `smooth` - a dict of mesh_smooth.smooth_mesh keyword arguments, e.g. dict(iterations=10) -
+        moves the vertices after `clean` and before `simplify` (one more host read): denoise, then decimate; None leaves
+        them where they were extracted."""
         L = _cabi.lib()
         a = self._mesh_args(min_weight)
         _cabi.check(L.mgs_tsdf_mesh_count(C.byref(a), stream_ptr(self.dev)), "mgs_tsdf_mesh_count")
@@ -392,6 +394,9 @@ class TSDFVolume:
         if clean is not None:
             from .mesh_clean import clean_mesh
             verts, faces, colors, _ = clean_mesh(verts, faces, colors, **clean)
+        if smooth is not None:
+            from .mesh_smooth import smooth_mesh
+            verts, _ = smooth_mesh(verts, faces, **smooth)
         if simplify is not None:
             from .mesh_simplify import simplify_keywords, simplify_mesh
             verts, faces, colors, _ = simplify_mesh(verts, faces, colors,
