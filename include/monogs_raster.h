@@ -1544,6 +1544,106 @@ uint64_t mgs_tsdf_mesh_scratch_bytes(int32_t nx, int32_t ny, int32_t nz);
 int32_t mgs_tsdf_mesh_count(const mgs_tsdf_mesh_args* args, void* stream);
 int32_t mgs_tsdf_mesh_emit(const mgs_tsdf_mesh_args* args, void* stream);
 
+/* ---- sparse TSDF volume ("Sparse TSDF volume") ---------------------------------------------------------
+ * The dense lattice above without its box: point (i,j,k), any sign, lies at origin + (i,j,k) * voxel_size, formed as
+ * above with the GLOBAL index.  A brick is 8 x 8 x 8 points, brick (bx,by,bz) holds i in [8 bx, 8 bx + 8) and likewise
+ * j, k; brick coordinates lie in [-2^20, 2^20) and pack into the key (bx + 2^20) | (by + 2^20) << 21 | (bz + 2^20) << 42.
+ * Storage is a caller-owned pool of max_bricks bricks (7 * 512 * max_bricks < 2^31, i.e. max_bricks <= 599186; more is
+ * MGS_ERR_UNSUPPORTED): tsdf [cap,512] (initial 1), weight [cap,512] (initial 0), color [3,cap,512] (initial 0), the
+ * local index of a point (lk * 8 + lj) * 8 + li; brick_coords int32 [cap,3]; the persistent map key -> brick id,
+ * map_keys uint64 [table_size] (initial all ones) and map_vals int32 [table_size], table_size =
+ * mgs_sparse_tsdf_table_size(max_bricks) (the smallest power of two >= 2 max_bricks); state int32 [4] (initial 0):
+ * [0] bricks allocated, [1] bricks not allocated for want of capacity (summed over the views), [2] candidates outside
+ * the coordinate range (summed), [3] new bricks the last view asked for.  The library keeps no state.
+ * The contract: a sparse volume is the dense volume of the same origin and voxel size in which every point of an
+ * unallocated brick has weight 0 (tsdf 1, colour 0).
+ *
+ * (a) mgs_sparse_tsdf_allocate: the bricks ONE view needs, no host read.  For every pixel (x, y) whose depth passes the
+ * tests of mgs_tsdf_integrate (d = depth[y,x]; with `opacity`: skip if o < min_opacity, and with `normalize` d = d / o;
+ * skip unless d > depth_min and d <= depth_max), for s in [0, samples) - samples = ceil(2 trunc / (4 vs)) + 1, formed
+ * by the caller - every operation a single fp32 rounding, in this order:
+ *   xn = (x - cx) / fx;  yn = (y - cy) / fy;  z = (d - trunc) + s * (4 * vs);  skip unless z > z_near;
+ *   q = (xn * z - t_0, yn * z - t_1, z - t_2);  world p_a = (R_0a q_0 + R_1a q_1) + R_2a q_2  (the transpose of T's
+ *   rotation);  l_a = (p_a - origin_a) / vs;  corner c in [0, 8): g_a = l_a + 4 if bit a of c else l_a - 4;
+ *   b_a = floor(g_a * 0.125).  A corner with some b_a outside [-2^20, 2^20) (tested in float; NaN is outside) is dropped
+ *   and counted in state[2].
+ * The candidate index is pixel * 8 samples + 8 s + c (pixel = y * width + x).  Candidates whose key the map holds are
+ * discarded; of the others the one of SMALLEST index represents its key; the representatives, in ascending candidate
+ * order, are the view's new bricks 0, 1, ...; new brick r gets id state[0] + r; ids >= max_bricks are not allocated and
+ * are counted in state[1].  The brick list is therefore a function of the inputs alone
+ * (sparse_tsdf.allocate_bricks_torch is the mirror).  `scratch`: mgs_sparse_tsdf_allocate_scratch_bytes, no initial
+ * state.  width * height * 8 * samples >= 2^31 is MGS_ERR_UNSUPPORTED.
+ *
+ * (b) mgs_sparse_tsdf_integrate: the update of mgs_tsdf_integrate, in its order of roundings, on every lattice point
+ * of every allocated brick (one workgroup per brick, the grid sized by max_bricks, workgroups past state[0] leave at
+ * once); the conservative brick cull of the dense kernel with its margins, on the brick's 8 x 8 x 8 corners.  No host
+ * read; `scratch` is not used. */
+typedef struct mgs_sparse_tsdf_volume {
+  int32_t max_bricks;        /* >= 1 */
+  int32_t reserved0;
+  float origin[3];
+  float voxel_size;          /* > 0 */
+  float* tsdf;               /* [cap,512] */
+  float* weight;             /* [cap,512] */
+  float* color;              /* [3,cap,512]; may be NULL where no colour is read or written */
+  int32_t* brick_coords;     /* [cap,3] */
+  uint64_t* map_keys;        /* [table_size] */
+  int32_t* map_vals;         /* [table_size] */
+  int32_t* state;            /* [4] */
+} mgs_sparse_tsdf_volume;
+
+typedef struct mgs_sparse_tsdf_view_args {
+  mgs_sparse_tsdf_volume vol;
+  int32_t width, height;
+  int32_t normalize;         /* d = d / o (needs `opacity`) */
+  int32_t samples;           /* allocate only: >= 1 */
+  float trunc;               /* > 0 */
+  float fx, fy, cx, cy;      /* fx, fy > 0 */
+  float z_near, depth_min, depth_max;
+  float min_opacity;
+  float view_weight;         /* integrate only: > 0 */
+  float max_weight;          /* integrate only: > 0 */
+  int32_t reserved0;
+  const float* T;            /* [4,4] row-major world -> camera, on the device */
+  const float* depth;        /* [H,W] */
+  const float* opacity;      /* [H,W] or NULL */
+  const float* image;        /* [3,H,W] or NULL (integrate only) */
+  void* scratch;             /* allocate only */
+} mgs_sparse_tsdf_view_args;
+
+int32_t mgs_sparse_tsdf_volume_size(void);
+int32_t mgs_sparse_tsdf_view_args_size(void);
+uint64_t mgs_sparse_tsdf_table_size(int32_t max_bricks);          /* 0 for a bad max_bricks */
+uint64_t mgs_sparse_tsdf_allocate_scratch_bytes(int32_t width, int32_t height, int32_t samples);   /* 0 for a bad size */
+int32_t mgs_sparse_tsdf_allocate(const mgs_sparse_tsdf_view_args* args, void* stream);
+int32_t mgs_sparse_tsdf_integrate(const mgs_sparse_tsdf_view_args* args, void* stream);
+/* Enters the bricks [first, first + count) of brick_coords (distinct, in range, not in the map: the caller's word) into
+ * the map with their own ids and sets state[0] = first + count: how a volume is built from a brick list. */
+int32_t mgs_sparse_tsdf_register(const mgs_sparse_tsdf_volume* vol, int32_t first, int32_t count, void* stream);
+
+/* (c) extraction: mgs_tsdf_mesh_count / _emit on the first num_bricks bricks (the caller has read state[0]).  Every
+ * cell, edge and triangle decision is the dense one; a point of an absent brick has the flags of a point outside a dense
+ * volume (not inside, no weight).  The virtual linear index of a point is brick * 512 + local: vertices come out in
+ * ascending (brick * 512 + local) * 7 + slot, faces by brick, cell, tetrahedron, triangle.
+ * `scratch` (mgs_sparse_tsdf_mesh_scratch_bytes(num_bricks)) carries the [num_bricks,27] neighbour table (brick ids,
+ * -1 where absent, entry (dx + 1) + 3 (dy + 1) + 9 (dz + 1)) and the classification from count to emit. */
+typedef struct mgs_sparse_tsdf_mesh_args {
+  mgs_sparse_tsdf_volume vol;
+  int32_t num_bricks;        /* 1 .. max_bricks, at most state[0] */
+  float min_weight;
+  void* scratch;
+  int32_t* counts;           /* [2] device (count only) */
+  float* verts;              /* [num_verts,3] (emit only) */
+  int32_t* faces;            /* [num_faces,3] (emit only) */
+  float* colors;             /* [num_verts,3] or NULL (emit only) */
+  int32_t num_verts, num_faces;   /* as read from counts (emit only) */
+} mgs_sparse_tsdf_mesh_args;
+
+int32_t mgs_sparse_tsdf_mesh_args_size(void);
+uint64_t mgs_sparse_tsdf_mesh_scratch_bytes(int32_t num_bricks);  /* 0 for a bad count */
+int32_t mgs_sparse_tsdf_mesh_count(const mgs_sparse_tsdf_mesh_args* args, void* stream);
+int32_t mgs_sparse_tsdf_mesh_emit(const mgs_sparse_tsdf_mesh_args* args, void* stream);
+
 /* ---- mesh clean-up ("Mesh clean-up") -------------------------------------------------------------------
  * Connected components of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL),
  * clusters kept by size, vertices / colours / faces compacted.  The NumPy mirror mesh_clean.clean_mesh_numpy is the

@@ -44,6 +44,10 @@ EXPORTS = (
     "mgs_surface_args_size", "mgs_surface_forward", "mgs_depth_normal_args_size", "mgs_depth_normal",
     "mgs_tsdf_integrate_args_size", "mgs_tsdf_integrate", "mgs_tsdf_mesh_args_size", "mgs_tsdf_mesh_scratch_bytes",
     "mgs_tsdf_mesh_count", "mgs_tsdf_mesh_emit",
+    "mgs_sparse_tsdf_volume_size", "mgs_sparse_tsdf_view_args_size", "mgs_sparse_tsdf_mesh_args_size",
+    "mgs_sparse_tsdf_table_size", "mgs_sparse_tsdf_allocate_scratch_bytes", "mgs_sparse_tsdf_allocate",
+    "mgs_sparse_tsdf_integrate", "mgs_sparse_tsdf_register", "mgs_sparse_tsdf_mesh_scratch_bytes",
+    "mgs_sparse_tsdf_mesh_count", "mgs_sparse_tsdf_mesh_emit",
     "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
     "mgs_mesh_components",
     "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
@@ -398,6 +402,32 @@ class TsdfMeshArgs(C.Structure):
                 + [("num_verts", C.c_int32), ("num_faces", C.c_int32)])
 
 
+SPARSE_TSDF_BRICK = 8                                    # points along a brick's edge
+SPARSE_TSDF_MAX_BRICKS = (2 ** 31 - 1) // (7 * 512)      # 7 * 512 * max_bricks < 2^31: 599186
+SPARSE_TSDF_COORD_RANGE = 2 ** 20                        # brick coordinates lie in [-2^20, 2^20)
+
+
+class SparseTsdfVolume(C.Structure):
+    _fields_ = ([("max_bricks", C.c_int32), ("reserved0", C.c_int32), ("origin", C.c_float * 3),
+                 ("voxel_size", C.c_float)]
+                + [(n, _fp) for n in ("tsdf", "weight", "color", "brick_coords", "map_keys", "map_vals", "state")])
+
+
+class SparseTsdfViewArgs(C.Structure):
+    _fields_ = ([("vol", SparseTsdfVolume)]
+                + [(n, C.c_int32) for n in ("width", "height", "normalize", "samples")]
+                + [(n, C.c_float) for n in ("trunc", "fx", "fy", "cx", "cy", "z_near", "depth_min", "depth_max",
+                                            "min_opacity", "view_weight", "max_weight")]
+                + [("reserved0", C.c_int32)]
+                + [(n, _fp) for n in ("T", "depth", "opacity", "image", "scratch")])
+
+
+class SparseTsdfMeshArgs(C.Structure):
+    _fields_ = ([("vol", SparseTsdfVolume), ("num_bricks", C.c_int32), ("min_weight", C.c_float)]
+                + [(n, _fp) for n in ("scratch", "counts", "verts", "faces", "colors")]
+                + [("num_verts", C.c_int32), ("num_faces", C.c_int32)])
+
+
 MESH_CLEAN_MAX_ITEMS = (2 ** 31 - 1) // 3     # 3 V, 3 F < 2^31: 32-bit element indices of the [n,3] arrays
 MESH_CLEAN_COUNTS = 5                         # V', F', clusters, kept clusters, bad faces
 
@@ -704,6 +734,21 @@ def lib():
     L.mgs_tsdf_integrate.restype, L.mgs_tsdf_integrate.argtypes = C.c_int32, [C.POINTER(TsdfIntegrateArgs), C.c_void_p]
     for fn in (L.mgs_tsdf_mesh_count, L.mgs_tsdf_mesh_emit):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(TsdfMeshArgs), C.c_void_p]
+    for fn, cls in ((L.mgs_sparse_tsdf_volume_size, SparseTsdfVolume), (L.mgs_sparse_tsdf_view_args_size, SparseTsdfViewArgs),
+                    (L.mgs_sparse_tsdf_mesh_args_size, SparseTsdfMeshArgs)):
+        fn.restype, fn.argtypes = C.c_int32, []
+        if fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+    for fn in (L.mgs_sparse_tsdf_table_size, L.mgs_sparse_tsdf_mesh_scratch_bytes):
+        fn.restype, fn.argtypes = C.c_uint64, [C.c_int32]
+    L.mgs_sparse_tsdf_allocate_scratch_bytes.restype = C.c_uint64
+    L.mgs_sparse_tsdf_allocate_scratch_bytes.argtypes = [C.c_int32, C.c_int32, C.c_int32]
+    for fn in (L.mgs_sparse_tsdf_allocate, L.mgs_sparse_tsdf_integrate):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(SparseTsdfViewArgs), C.c_void_p]
+    L.mgs_sparse_tsdf_register.restype = C.c_int32
+    L.mgs_sparse_tsdf_register.argtypes = [C.POINTER(SparseTsdfVolume), C.c_int32, C.c_int32, C.c_void_p]
+    for fn in (L.mgs_sparse_tsdf_mesh_count, L.mgs_sparse_tsdf_mesh_emit):
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(SparseTsdfMeshArgs), C.c_void_p]
     L.mgs_mesh_clean_args_size.restype, L.mgs_mesh_clean_args_size.argtypes = C.c_int32, []
     if L.mgs_mesh_clean_args_size() != C.sizeof(MeshCleanArgs):
         raise NativeLibraryError("MeshCleanArgs does not have the size of mgs_mesh_clean_args")

@@ -282,7 +282,8 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
-              cull=None, normals: bool = False, preview=None, simplify=None, smooth=None, topology: bool = False, **fuse_kw):
+              cull=None, normals: bool = False, preview=None, simplify=None, smooth=None, topology: bool = False, sparse=None,
+              **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -300,18 +301,24 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     after `clean` and before the normals, the preview and the scores, so that all three describe the file written.
     `smooth` - a dict of mesh_smooth.smooth_mesh keyword arguments, e.g. dict(iterations=10) - moves the vertices after
     `clean` and before `simplify`.  `topology=True` writes mesh_topology.json next to mesh.ply: the dict of
-    mesh_topology.mesh_topology(faces, V, components=True) for the mesh as written."""
+    mesh_topology.mesh_topology(faces, V, components=True) for the mesh as written.  A
+    sparse_tsdf.SparseTSDFVolume is extracted as it stands, too; `sparse` - True, or dict(max_bricks=, origin=) - fuses a
+    Gaussian model into one (tsdf.fuse_map's `sparse`)."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
         return None
     vol = gaussians_or_volume
-    if not isinstance(vol, tsdf.TSDFVolume):
+    from .sparse_tsdf import SparseTSDFVolume
+    if not isinstance(vol, (tsdf.TSDFVolume, SparseTSDFVolume)):
         if cameras is None:
             raise ValueError("save_mesh: a Gaussian model needs the cameras to fuse from")
         if background is None:
             background = torch.zeros(3, device=vol.get_xyz.device)
-        vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
+        if sparse is not None and sparse is not False:
+            vol = tsdf.fuse_map(vol, cameras, background, voxel_size, sparse=sparse, **fuse_kw)
+        else:
+            vol = tsdf.fuse_map(vol, cameras, background, voxel_size, margin=margin, **fuse_kw)
     if smooth is not None:
         verts, faces, colors = vol.extract_mesh(min_weight, clean=clean, simplify=simplify, smooth=smooth)
     elif simplify is not None:

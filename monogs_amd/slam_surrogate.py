@@ -176,7 +176,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
                  native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
                  stereo_matcher=None, second_order_exact: bool = False, viewer_every: int = 0,
-                 viewer_modes=("rgb",), viewer_follow: bool = True):
+                 viewer_modes=("rgb",), viewer_follow: bool = True, mesh_volume=None, mesh_every: int = 1):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -214,7 +214,13 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     viewer.NativeViewer takes one frame per mode of `viewer_modes` of the map as it then is - from the follow-camera
     behind the tracked pose (`viewer_follow`) or from the tracked camera itself - with the keyframe frusta, the current
     camera and the trajectory so far drawn over it; the result then also holds `view_frames`:
-    {frame id: {mode: uint8 [H,W,3] device tensor}}.  Tracking and mapping never read anything the viewer writes."""
+    {frame id: {mode: uint8 [H,W,3] device tensor}}.  Tracking and mapping never read anything the viewer writes.
+    `mesh_volume`: a caller-owned sparse_tsdf.SparseTSDFVolume; every `mesh_every`-th keyframe (the first frame is
+    keyframe 0) is integrated into it as the run goes, after its mapping and outside the timed sections - from the
+    frame's sensor depth with the camera's image when there is one (`sensor_depth`, a stereo matcher), else from the
+    map's rendered view at the keyframe's pose (integrate_view) - which a dense box, sized from a finished map, cannot
+    serve.  The result then also holds `mesh_keyframes`, the keyframes fused.  Tracking and mapping read nothing the
+    volume writes; None leaves the run as it is."""
     if stereo_matcher is not None:
         if any(getattr(f, "image_right", None) is None for f in frames):
             raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
@@ -313,6 +319,23 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             raise RuntimeError("viewer: pair capacity still exceeded after growing the workspaces three times")
         view_frames[k] = shots
 
+    mesh_keyframes, n_keyframes = [], 0
+
+    def fuse_keyframe(k, fr):
+        """Keyframe k into `mesh_volume` (every mesh_every-th one): outside the timed sections."""
+        nonlocal n_keyframes
+        n_keyframes += 1
+        if mesh_volume is None or (n_keyframes - 1) % max(1, int(mesh_every)) != 0:
+            return
+        v = cams[k]
+        if sensor_depth:
+            img = v.original_image
+            img = img if torch.is_tensor(img) and img.dtype == torch.float32 and img.dim() == 3 else None
+            mesh_volume.integrate(depth_of(fr), v.T.detach(), v.fx, v.fy, v.cx, v.cy, image=img)
+        else:
+            mesh_volume.integrate_view(gm, v, bg)
+        mesh_keyframes.append(k)
+
     t_track = t_map = 0.0
     n_track_iters = n_map_iters = n_map_views = 0
     cams = {}
@@ -327,6 +350,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     mapper.initialize_map(0, iters=init_iters)
     torch.cuda.synchronize()
     t_init = time.perf_counter() - t0
+    fuse_keyframe(0, f0)
     window = [0]
     kf_ids = [0]
     last_kf = 0
@@ -380,6 +404,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                 t_init += time.perf_counter() - t0
                 window, kf_ids, last_kf = [k], [k], k
                 windows.append(list(window))
+                fuse_keyframe(k, fr)
                 if viewer_every > 0 and k % viewer_every == 0:
                     take_views(k)
                 continue
@@ -403,6 +428,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             n_map_views += iters * (len(window) + min(2, len(kf_ids) - len(window)))
             if log:
                 log(f"keyframe {k}: window {window}, {len(gm)} Gaussians, loss {float(mapper.last_loss):.4f}")
+            fuse_keyframe(k, fr)
         windows.append(list(window))
         if viewer_every > 0 and k % viewer_every == 0:
             take_views(k)
@@ -417,6 +443,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         result["t_prepare"] = t_prepare
     if viewer_every > 0:
         result["view_frames"] = view_frames
+    if mesh_volume is not None:
+        result["mesh_keyframes"] = mesh_keyframes
     return result
 
 
@@ -474,7 +502,7 @@ def evaluate(result, frames, dev, every: int = 1, monocular: bool = True, native
 
 
 def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_depth=None, margin: float = 0.1,
-                     min_weight: float = 1.0, clean=None, simplify=None, smooth=None, **fuse_kw):
+                     min_weight: float = 1.0, clean=None, simplify=None, smooth=None, sparse=None, **fuse_kw):
     """The surface of a finished run: fuses every `every_keyframe`-th keyframe of a run_sequence `result` (its
     "cameras", "kf_ids", "gaussians") into a tsdf.TSDFVolume sized from the map and extracts the mesh:
     (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32) on the device.  By default each keyframe contributes the map's
@@ -485,11 +513,24 @@ def reconstruct_mesh(result, voxel_size: float, every_keyframe: int = 1, sensor_
     `simplify` - a dict of mesh_simplify.simplify_mesh keyword arguments, e.g. dict(factor=2) for cells of two voxels -
     merges the vertices of every cell afterwards (TSDFVolume.extract_mesh).  `smooth` - a dict of
     mesh_smooth.smooth_mesh keyword arguments, e.g. dict(iterations=10) - moves the vertices after `clean` and before
-    `simplify`."""
+    `simplify`.  `sparse` - True, or dict(max_bricks=, origin=) - fuses into a sparse_tsdf.SparseTSDFVolume instead
+    (tsdf.fuse_map's `sparse`): no bounds pass, no `margin`, memory by the surface seen."""
     from . import tsdf
     gm = result["gaussians"]
     ids = list(result["kf_ids"])[::max(1, int(every_keyframe))]
     cams = [result["cameras"][k] for k in ids]
+    if sparse is not None and sparse is not False:
+        if sensor_depth is None:
+            vol = tsdf.fuse_map(gm, cams, torch.zeros(3, device=gm.get_xyz.device), voxel_size, sparse=sparse, **fuse_kw)
+        else:
+            vol = tsdf.sparse_volume(sparse, voxel_size, gm.get_xyz.device, trunc=fuse_kw.get("trunc"),
+                                     max_weight=fuse_kw.get("max_weight", 64.0))
+            for k, cam in zip(ids, cams):
+                img = cam.original_image
+                img = img if torch.is_tensor(img) and img.dtype == torch.float32 and img.dim() == 3 else None
+                vol.integrate(sensor_depth[k], cam.T, cam.fx, cam.fy, cam.cx, cam.cy, image=img,
+                              depth_max=fuse_kw.get("depth_max", math.inf))
+        return vol.extract_mesh(min_weight, clean=clean, simplify=simplify, smooth=smooth)
     if sensor_depth is None:
         bg = torch.zeros(3, device=gm.get_xyz.device)
         vol = tsdf.fuse_map(gm, cams, bg, voxel_size, margin=margin, **fuse_kw)

@@ -404,12 +404,27 @@ class TSDFVolume:
         return verts, faces, colors
 
 
+def sparse_volume(sparse, voxel_size: float, device, trunc=None, max_weight: float = 64.0):
+    """The sparse_tsdf.SparseTSDFVolume that `sparse` - True, or dict(max_bricks=, origin=) - asks for."""
+    from .sparse_tsdf import SparseTSDFVolume
+    kw = {} if sparse is True else dict(sparse)
+    unknown = set(kw) - {"max_bricks", "origin"}
+    if unknown:
+        raise ValueError(f"sparse: unknown keys {sorted(unknown)} (max_bricks, origin)")
+    return SparseTSDFVolume(kw.get("origin", (0.0, 0.0, 0.0)), voxel_size, kw.get("max_bricks", 65536), trunc=trunc,
+                            device=device, max_weight=max_weight)
+
+
 def fuse_map(gaussians, cameras: Iterable, background, voxel_size: float, margin: float = 0.1, trunc=None,
              max_weight: float = 64.0, min_opacity: float = 0.95, depth_max: float = math.inf,
-             volume: Optional[TSDFVolume] = None, depth_mode: str = "mean") -> TSDFVolume:
-    """Fuses the map's own rendered depth at `cameras` into a volume sized from the map (or into `volume`):
-    depth / opacity with depth_mode "mean", the median depth with "median" (TSDFVolume.integrate_view)."""
+             volume=None, depth_mode: str = "mean", sparse=None):
+    """Fuses the map's own rendered depth at `cameras` into a volume sized from the map (or into `volume`, a TSDFVolume
+    or a sparse_tsdf.SparseTSDFVolume): depth / opacity with depth_mode "mean", the median depth with "median"
+    (TSDFVolume.integrate_view).  `sparse` - True, or dict(max_bricks=, origin=) - fuses into a new SparseTSDFVolume
+    instead: no bounds pass over the map, `margin` is not used, and the bricks come with the views."""
     vol = volume
+    if vol is None and sparse is not None and sparse is not False:
+        vol = sparse_volume(sparse, voxel_size, gaussians.get_xyz.device, trunc=trunc, max_weight=max_weight)
     if vol is None:
         vol = TSDFVolume.for_map(gaussians, voxel_size, margin, trunc=trunc, max_weight=max_weight)
     for cam in cameras:
