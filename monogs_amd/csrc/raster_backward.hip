@@ -61,9 +61,11 @@ __device__ __forceinline__ int pair_slot_base(const KP& P, int idx) {
 
 // ---------------------------------------------------------------------------------
 // Blend backward, item-parallel.  One wave per work item = kItem consecutive splats of one tile's
-// list, FOUR pixels per lane, one in each 8x8 quadrant of the tile.  The lane that stages a splat
-// also evaluates the culling bound on the four quadrant boxes; the wave then visits, per
-// splat, only the quadrants that can be reached (wave-uniform scalar bit tests on ballot masks).
+// list, FOUR pixels per lane, one in each 8x8 quadrant of the tile.  Which quadrants a splat can
+// reach is NOT evaluated here: the forward's quadrant waves ran the exact box test and left, per
+// item, one reach word per quadrant (P.reach) and, per tile, each quadrant's last contributing list
+// position (P.quad_last); the wave visits, per splat, only the quadrants whose reach bit is set and
+// that are not yet saturated (wave-uniform scalar bit tests on those words).
 // The quadrant body is written on float2 operands so that it maps onto v_pk_{add,mul,fma}_f32
 // (measured on gfx950: a packed FMA issues in about 1.25x the time of a scalar one).  The forward
 // checkpointed the per-pixel blend state (T, prefix colour F) in front of every segment, so items

@@ -54,6 +54,14 @@ CONSTANTS = dict(
     w_eps=1e-7,            # p_w = 1/(p_hom.w + 1e-7)
 )
 
+# Mutation points for tests/raster_parity.py, which builds deliberately WRONG variants of this oracle to
+# show that its comparison rejects them.  Both stay None everywhere else.
+#   order(tx, ty, ids) -> ids     reorders one tile's depth-sorted list
+#   touch(tx, ty, PX, PY) -> bool[256]   pixels of the tile whose n_touched contributions are kept
+# and one observer, for measuring how far the raw alpha of two precisions differs on the pairs that are blended:
+#   pairs(tx, ty, ids, raw, include)      raw alpha o exp(power) [n,256] and the blended-pair mask of a tile
+HOOKS = dict(order=None, touch=None, pairs=None)
+
 SH_C0 = 0.28209479177387814
 SH_C1 = 0.4886025119029199
 SH_C2 = (1.0925484305920792, -1.0925484305920792, 0.31539156525252005,
@@ -343,6 +351,8 @@ def composite(proj: Projected, settings: RasterSettings):
             # stable sort by depth; ties keep ascending Gaussian index
             order = torch.sort(depth_d[sel], stable=True).indices
             ids = ids[order]
+            if HOOKS["order"] is not None:
+                ids = HOOKS["order"](tx, ty, ids)
             ys = torch.arange(ty * B, ty * B + B, dtype=dt)
             xs = torch.arange(tx * B, tx * B + B, dtype=dt)
             PY, PX = torch.meshgrid(ys, xs, indexing="ij")
@@ -373,6 +383,10 @@ def composite(proj: Projected, settings: RasterSettings):
                 O = (1.0 - T_fin).detach()
                 touched = include & (T_incl.detach() > K["touch_t"])
                 inside = (PX < W) & (PY < H)
+                if HOOKS["pairs"] is not None:
+                    HOOKS["pairs"](tx, ty, ids, raw.detach(), include & inside[None, :])
+                if HOOKS["touch"] is not None:
+                    inside = inside & HOOKS["touch"](tx, ty, PX, PY)
                 n_touched.index_add_(0, ids, (touched & inside[None, :]).sum(dim=1))
             row_img.append(C.reshape(3, B, B))
             row_dep.append(D.reshape(1, B, B))

@@ -4,6 +4,10 @@ autograd oracle (small sizes) and the C++ host emulation (full BASELINE sizes).
 Tolerances (BASELINE.json north_star): forward image L1 <= 1e-4; backward gradients
 <= 1e-3 relative (norm-wise: the alpha>=1/255 and T<1e-4 cut-offs are discontinuous, so a
 handful of (pixel, splat) pairs may flip between two fp32 implementations).
+
+These are aggregates: they do not see a few dropped pairs or wrong small gradient rows.  The per-pixel / per-row
+comparison with the oracle's own flip allowance is tests/test_gpu_raster_parity.py (helper tests/raster_parity.py;
+DESIGN.md section 2, "How parity is held").
 """
 import pytest
 import numpy as np
