@@ -1644,6 +1644,112 @@ uint64_t mgs_sparse_tsdf_mesh_scratch_bytes(int32_t num_bricks);  /* 0 for a bad
 int32_t mgs_sparse_tsdf_mesh_count(const mgs_sparse_tsdf_mesh_args* args, void* stream);
 int32_t mgs_sparse_tsdf_mesh_emit(const mgs_sparse_tsdf_mesh_args* args, void* stream);
 
+/* ---- ray cast of the volumes ("Ray cast of the volumes") ------------------------------------------------
+ * Depth, normal and colour of the fused surface at a pose, from a dense or a sparse volume, without a mesh and without
+ * a host read.  The torch mirror tsdf_raycast.raycast_torch is the contract; the device equals it bit for bit: every
+ * pixel is independent and every operation below is a single fp32 rounding.
+ *   Ray       pixel (x, y): xn = (x - cx) / fx, yn = (y - cy) / fy.  Samples in camera z: z_n = z_near + n * dz for
+ *             n in [0, num_steps); dz = f32(step) * f32(voxel_size) and num_steps = floor((z_far - z_near) / dz) + 1
+ *             are formed by the caller; 2 <= num_steps <= 2^20.  World point as mgs_sparse_tsdf_allocate forms it:
+ *             q = (xn z - t_0, yn z - t_1, z - t_2), p_a = (R_0a q_0 + R_1a q_1) + R_2a q_2, l_a = (p_a - origin_a) / vs.
+ *   Sample    b_a = floor(l_a); invalid unless every |b_a| < 2^23 (tested in float: a NaN is invalid); f_a = l_a - b_a.
+ *             The eight points b + d, d in {0,1}^3, must each have weight >= min_weight (false for NaN).  A point
+ *             outside the dense box, of an unallocated brick or of a brick coordinate outside [-2^20, 2^20) has weight
+ *             0.  The value is lerp(a, b, f) = a + f * (b - a) along x, then y, then z.
+ *   March     n ascending.  At a valid sample whose predecessor n - 1 was valid: f_prev > 0 && f <= 0 is a HIT;
+ *             f_prev < 0 && f > 0 ends the ray as a back face (a miss); anything else continues.  Running out of n is
+ *             a miss.
+ *   Outputs   hit: t = f_prev / (f_prev - f), depth = z_{n-1} + t * dz, hit_step = n.  Miss: depth 0, normal and
+ *             colour 0, hit_step -1 (ran out) or -2 (back face).
+ *   At a hit  l* is formed again from `depth` by the sample expression.  Colour: the trilinear sample of the three
+ *             colour planes at l* (0 without colour planes).  Gradient g_a = value(l* + e_a) - value(l* - e_a), the
+ *             offset added to l_a in fp32.  L = sqrt((g_0^2 + g_1^2) + g_2^2).  If the sample at l* or one of the six
+ *             is invalid, or L is not a finite value > 0, colour and normal are 0; otherwise normal = g / L (as
+ *             mgs_face_normals), which points to the positive-TSDF side, and with frame MGS_RAYCAST_FRAME_CAMERA it is
+ *             turned by T's rotation, n_r = (R_r0 n_0 + R_r1 n_1) + R_r2 n_2.
+ *   skip      1: samples proved invalid (the base point's brick is absent; the ray is outside the dense box) are
+ *             passed over; the result is the one of skip = 0, which evaluates every n.
+ * One wave owns an 8 x 8 pixel tile.  The sparse ray cast reads the [max_bricks,27] neighbour table in `scratch`
+ * (mgs_sparse_tsdf_raycast_scratch_bytes(max_bricks), 0 for a bad count); with build_table = 1 a launch over the pool
+ * (entries past 27 * state[0] leave) writes it first - the caller asks for that whenever bricks were added since.  An
+ * entry outside [0, max_bricks) is read as absent.
+ * A null struct or needed array, H or W < 1, fx or fy not > 0, dz not > 0, a frame or skip outside {0, 1}, num_steps < 2:
+ * MGS_ERR_BAD_ARGUMENT.  num_steps > 2^20, H * W >= 2^31 / 3: MGS_ERR_UNSUPPORTED.  A refused call launches nothing.
+ *
+ * mgs_raycast_shade: out [H,W,3] u8 from the ray cast's planes (normal in the CAMERA frame), one launch, one lane per
+ * pixel.  A miss (hit_step < 0) gets `background`.  Channels are quantised as MGS_VIEW_RGB does.
+ *   MGS_RAYCAST_SHADE_SHADED  grey 0.25 + 0.75 |n.z| (mgs_mesh_shade's headlight)
+ *   MGS_RAYCAST_SHADE_NORMAL  0.5 n + 0.5 with n negated when (n.x rx + n.y ry) + n.z > 0, r the pixel's ray
+ *   MGS_RAYCAST_SHADE_COLOR   the colour plane
+ *   MGS_RAYCAST_SHADE_DEPTH   t = (d - lo) / (hi - lo), out = lut[min(255, (int)(clamp(t, 0, 1) * 256))]: MGS_VIEW_DEPTH's
+ *                             rule with the range [lo, hi] given by the caller (the ray cast's z_near and z_far) in place
+ *                             of the plane's maximum, which would cost a launch; a NaN is black */
+#define MGS_RAYCAST_FRAME_CAMERA 0
+#define MGS_RAYCAST_FRAME_WORLD 1
+#define MGS_RAYCAST_MAX_STEPS (1 << 20)
+#define MGS_RAYCAST_SHADE_SHADED 0
+#define MGS_RAYCAST_SHADE_NORMAL 1
+#define MGS_RAYCAST_SHADE_COLOR 2
+#define MGS_RAYCAST_SHADE_DEPTH 3
+
+typedef struct mgs_raycast_view {
+  int32_t width, height;
+  int32_t num_steps;         /* N: 2 .. 2^20 */
+  int32_t frame;             /* MGS_RAYCAST_FRAME_* */
+  int32_t skip;              /* 0 or 1 */
+  int32_t reserved0;
+  float fx, fy, cx, cy;      /* fx, fy > 0 */
+  float z_near, dz;          /* dz > 0 */
+  float min_weight;
+  int32_t reserved1;
+  const float* T;            /* [4,4] row-major world -> camera, on the device */
+  float* depth;              /* [H,W] out */
+  float* normal;             /* [H,W,3] out */
+  float* color;              /* [H,W,3] out */
+  int32_t* hit_step;         /* [H,W] out */
+  int32_t* evaluated;        /* [H,W] out or NULL: the samples the march evaluated - a diagnostic, it depends on skip */
+} mgs_raycast_view;
+
+typedef struct mgs_tsdf_raycast_args {
+  int32_t nx, ny, nz, reserved0;
+  float origin[3];
+  float voxel_size;          /* > 0 */
+  const float* tsdf;         /* [nz,ny,nx] */
+  const float* weight;       /* [nz,ny,nx] */
+  const float* color;        /* [3,nz,ny,nx] or NULL */
+  mgs_raycast_view view;
+} mgs_tsdf_raycast_args;
+
+typedef struct mgs_sparse_tsdf_raycast_args {
+  mgs_sparse_tsdf_volume vol;
+  mgs_raycast_view view;
+  void* scratch;             /* the neighbour table */
+  int32_t build_table;       /* 1: write the table before the ray cast */
+  int32_t reserved0;
+} mgs_sparse_tsdf_raycast_args;
+
+typedef struct mgs_raycast_shade_args {
+  int32_t width, height;
+  int32_t mode;              /* MGS_RAYCAST_SHADE_* */
+  float fx, fy, cx, cy;      /* NORMAL; fx, fy > 0 */
+  float depth_lo, depth_hi;  /* DEPTH */
+  uint8_t background[4];     /* r, g, b, spare */
+  const float* depth;        /* [H,W] (DEPTH) */
+  const float* normal;       /* [H,W,3] camera frame (SHADED, NORMAL) */
+  const float* color;        /* [H,W,3] (COLOR) */
+  const int32_t* hit_step;   /* [H,W] */
+  const uint8_t* lut;        /* [256,3] (DEPTH) */
+  uint8_t* out;              /* [H,W,3] */
+} mgs_raycast_shade_args;
+
+int32_t mgs_tsdf_raycast_args_size(void);
+int32_t mgs_sparse_tsdf_raycast_args_size(void);
+int32_t mgs_raycast_shade_args_size(void);
+uint64_t mgs_sparse_tsdf_raycast_scratch_bytes(int32_t max_bricks);
+int32_t mgs_tsdf_raycast(const mgs_tsdf_raycast_args* args, void* stream);
+int32_t mgs_sparse_tsdf_raycast(const mgs_sparse_tsdf_raycast_args* args, void* stream);
+int32_t mgs_raycast_shade(const mgs_raycast_shade_args* args, void* stream);
+
 /* ---- mesh clean-up ("Mesh clean-up") -------------------------------------------------------------------
  * Connected components of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL),
  * clusters kept by size, vertices / colours / faces compacted.  The NumPy mirror mesh_clean.clean_mesh_numpy is the

@@ -48,6 +48,8 @@ EXPORTS = (
     "mgs_sparse_tsdf_table_size", "mgs_sparse_tsdf_allocate_scratch_bytes", "mgs_sparse_tsdf_allocate",
     "mgs_sparse_tsdf_integrate", "mgs_sparse_tsdf_register", "mgs_sparse_tsdf_mesh_scratch_bytes",
     "mgs_sparse_tsdf_mesh_count", "mgs_sparse_tsdf_mesh_emit",
+    "mgs_tsdf_raycast_args_size", "mgs_sparse_tsdf_raycast_args_size", "mgs_raycast_shade_args_size",
+    "mgs_sparse_tsdf_raycast_scratch_bytes", "mgs_tsdf_raycast", "mgs_sparse_tsdf_raycast", "mgs_raycast_shade",
     "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
     "mgs_mesh_components",
     "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
@@ -428,6 +430,34 @@ class SparseTsdfMeshArgs(C.Structure):
                 + [("num_verts", C.c_int32), ("num_faces", C.c_int32)])
 
 
+RAYCAST_FRAME_CAMERA, RAYCAST_FRAME_WORLD = 0, 1          # MGS_RAYCAST_FRAME_*
+RAYCAST_MAX_STEPS = 1 << 20                              # MGS_RAYCAST_MAX_STEPS
+RAYCAST_SHADE_SHADED, RAYCAST_SHADE_NORMAL, RAYCAST_SHADE_COLOR, RAYCAST_SHADE_DEPTH = 0, 1, 2, 3     # MGS_RAYCAST_SHADE_*
+
+
+class RaycastView(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "num_steps", "frame", "skip", "reserved0")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "z_near", "dz", "min_weight")]
+                + [("reserved1", C.c_int32)]
+                + [(n, _fp) for n in ("T", "depth", "normal", "color", "hit_step", "evaluated")])
+
+
+class TsdfRaycastArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("nx", "ny", "nz", "reserved0")] + [("origin", C.c_float * 3)]
+                + [("voxel_size", C.c_float)] + [(n, _fp) for n in ("tsdf", "weight", "color")] + [("view", RaycastView)])
+
+
+class SparseTsdfRaycastArgs(C.Structure):
+    _fields_ = [("vol", SparseTsdfVolume), ("view", RaycastView), ("scratch", _fp), ("build_table", C.c_int32),
+                ("reserved0", C.c_int32)]
+
+
+class RaycastShadeArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "mode")]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "depth_lo", "depth_hi")] + [("background", C.c_uint8 * 4)]
+                + [(n, _fp) for n in ("depth", "normal", "color", "hit_step", "lut", "out")])
+
+
 MESH_CLEAN_MAX_ITEMS = (2 ** 31 - 1) // 3     # 3 V, 3 F < 2^31: 32-bit element indices of the [n,3] arrays
 MESH_CLEAN_COUNTS = 5                         # V', F', clusters, kept clusters, bad faces
 
@@ -749,6 +779,15 @@ def lib():
     L.mgs_sparse_tsdf_register.argtypes = [C.POINTER(SparseTsdfVolume), C.c_int32, C.c_int32, C.c_void_p]
     for fn in (L.mgs_sparse_tsdf_mesh_count, L.mgs_sparse_tsdf_mesh_emit):
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(SparseTsdfMeshArgs), C.c_void_p]
+    for size_fn, cls, fn in ((L.mgs_tsdf_raycast_args_size, TsdfRaycastArgs, L.mgs_tsdf_raycast),
+                             (L.mgs_sparse_tsdf_raycast_args_size, SparseTsdfRaycastArgs, L.mgs_sparse_tsdf_raycast),
+                             (L.mgs_raycast_shade_args_size, RaycastShadeArgs, L.mgs_raycast_shade)):
+        size_fn.restype, size_fn.argtypes = C.c_int32, []
+        if size_fn() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} layout mismatch: library {size_fn()} bytes, ctypes {C.sizeof(cls)}")
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
+    L.mgs_sparse_tsdf_raycast_scratch_bytes.restype = C.c_uint64
+    L.mgs_sparse_tsdf_raycast_scratch_bytes.argtypes = [C.c_int32]
     L.mgs_mesh_clean_args_size.restype, L.mgs_mesh_clean_args_size.argtypes = C.c_int32, []
     if L.mgs_mesh_clean_args_size() != C.sizeof(MeshCleanArgs):
         raise NativeLibraryError("MeshCleanArgs does not have the size of mgs_mesh_clean_args")

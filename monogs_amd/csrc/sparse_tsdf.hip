@@ -31,18 +31,14 @@
 #include "pinhole.h"
 #include "rn_math.h"
 #include "scratch_carve.h"
+#include "sparse_tsdf_map.h"
 
 namespace mgs {
 namespace sparse {
 
-constexpr int kThreads = 256;
 static_assert(kThreads == kCompactThreads, "block_scan2 scans a workgroup of kCompactThreads");
-constexpr int kB = 8, kBP = kB * kB * kB;                  // brick edge, points of a brick
 constexpr int kH = kB + 2, kC = kB + 1;                    // flag tile with its halo; cells with base corner -1 .. 7
 constexpr int kIntThreads = kBP / 4;                       // integration: four points per thread
-constexpr int kBias = 1 << 20;                             // brick coordinates lie in [-kBias, kBias)
-constexpr int kMaxBricks = (int)(((1ll << 31) - 1) / (7 * kBP));      // 7 * 512 * bricks < 2^31: 599186
-constexpr unsigned long long kNoKey = ~0ull;               // no brick key has bit 63
 constexpr unsigned short kNoRank = 0xFFFFu;
 constexpr int kLocalSlots = 2 * kThreads;                  // a block's own set in k_alloc_insert: twice its candidates
 
@@ -62,36 +58,7 @@ __device__ __constant__ unsigned char c_tet_tri[16][6] = {
 // TET_TABLE_END
 __device__ __constant__ unsigned char c_tet_edge[6][2] = {{0, 1}, {0, 2}, {0, 3}, {1, 2}, {1, 3}, {2, 3}};
 
-__device__ __forceinline__ float lattice(float o, int i, float vs) { return add_rn(o, mul_rn((float)i, vs)); }
-
-// ---- brick keys and the persistent map -------------------------------------------------------------------------------
-__host__ __device__ __forceinline__ bool coord_ok(int b) { return b >= -kBias && b < kBias; }
-__host__ __device__ __forceinline__ unsigned long long key_of(int bx, int by, int bz) {
-  return (unsigned long long)(bx + kBias) | (unsigned long long)(by + kBias) << 21 | (unsigned long long)(bz + kBias) << 42;
-}
-__device__ __forceinline__ void coords_of(unsigned long long key, int b[3]) {
-#pragma unroll
-  for (int a = 0; a < 3; a++) b[a] = (int)((key >> (21 * a)) & 0x1FFFFFull) - kBias;
-}
-
-// the key plane in the type of the 64-bit atomics
-__device__ __forceinline__ unsigned long long* keys_of(const mgs_sparse_tsdf_volume& v) {
-  static_assert(sizeof(unsigned long long) == sizeof(uint64_t), "brick keys are 64-bit");
-  return reinterpret_cast<unsigned long long*>(v.map_keys);
-}
-
-// the id of `key`, -1 when the map does not hold it; plain loads: the map was written by an earlier launch
-__device__ __forceinline__ int map_find(const unsigned long long* __restrict__ keys, const int* __restrict__ vals, unsigned mask,
-                                        unsigned long long key) {
-  unsigned slot = (unsigned)mix64(key) & mask;
-  for (unsigned probe = 0; probe <= mask; probe++, slot = (slot + 1) & mask) {
-    const unsigned long long cur = keys[slot];
-    if (cur == kNoKey) return -1;
-    if (cur == key) return vals[slot];
-  }
-  return -1;
-}
-
+// ---- the write side of the persistent map (sparse_tsdf_map.h has the keys and the read side) ------------------------
 // `key` (which no other thread of this launch inserts and the map does not hold) takes the first free slot of its
 // probe sequence; at most max_bricks <= table_size / 2 keys are ever inserted, so a free slot is met
 __device__ __forceinline__ void map_insert(unsigned long long* __restrict__ keys, int* __restrict__ vals, unsigned mask,
@@ -425,11 +392,7 @@ __global__ __launch_bounds__(kThreads) void k_sparse_neighbors(mgs_sparse_tsdf_v
                                                                unsigned map_mask) {
   const int e = blockIdx.x * kThreads + threadIdx.x;
   if (e >= 27 * bricks) return;
-  const int brick = e / 27, q = e - 27 * brick;
-  const int bx = V.brick_coords[3 * brick] + q % 3 - 1, by = V.brick_coords[3 * brick + 1] + (q / 3) % 3 - 1,
-            bz = V.brick_coords[3 * brick + 2] + q / 9 - 1;
-  int id = -1;
-  if (coord_ok(bx) && coord_ok(by) && coord_ok(bz)) id = map_find(keys_of(V), V.map_vals, map_mask, key_of(bx, by, bz));
+  const int id = neighbor_find(V, e, map_mask);
   nbr[e] = id < bricks ? id : -1;      // a brick past the count the caller read does not exist for this extraction
 }
 
@@ -617,18 +580,6 @@ __global__ __launch_bounds__(kThreads) void k_sparse_emit(mgs_sparse_tsdf_mesh_a
 }
 
 // ---- host checks -----------------------------------------------------------------------------------------------------
-static bool bricks_ok(int n) { return n >= 1 && n <= kMaxBricks; }
-
-static int32_t volume_status(const mgs_sparse_tsdf_volume* v) {
-  if (!v || v->max_bricks < 1) return MGS_ERR_BAD_ARGUMENT;
-  if (!v->tsdf || !v->weight || !v->brick_coords || !v->map_keys || !v->map_vals || !v->state) return MGS_ERR_BAD_ARGUMENT;
-  if (!(v->voxel_size > 0.f)) return MGS_ERR_BAD_ARGUMENT;
-  if (v->max_bricks > kMaxBricks) return MGS_ERR_UNSUPPORTED;
-  return MGS_OK;
-}
-
-static unsigned map_mask_of(const mgs_sparse_tsdf_volume& v) { return (unsigned)(set_table_size((unsigned long long)v.max_bricks) - 1); }
-
 static int32_t view_status(const mgs_sparse_tsdf_view_args* a) {
   if (!a) return MGS_ERR_BAD_ARGUMENT;
   const int32_t rc = volume_status(&a->vol);

@@ -283,7 +283,7 @@ def save_gaussians(gaussians, name, iteration, final: bool = False):
 def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cameras=None, background=None,
               voxel_size: float = 0.02, margin: float = 0.1, min_weight: float = 1.0, clean=None, gt=None, eval_kw=None,
               cull=None, normals: bool = False, preview=None, simplify=None, smooth=None, topology: bool = False, sparse=None,
-              **fuse_kw):
+              volume_preview=None, volume_preview_kw=None, **fuse_kw):
     """The map's surface next to its point cloud: <name>/point_cloud/final/mesh.ply (or iteration_<n>), where
     save_gaussians puts point_cloud.ply.  A tsdf.TSDFVolume is extracted as it stands; a Gaussian model is first fused
     from its own rendered depth at `cameras` (tsdf.fuse_map, which takes `fuse_kw`: depth_mode="median" fuses the median
@@ -303,7 +303,10 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
     `clean` and before `simplify`.  `topology=True` writes mesh_topology.json next to mesh.ply: the dict of
     mesh_topology.mesh_topology(faces, V, components=True) for the mesh as written.  A
     sparse_tsdf.SparseTSDFVolume is extracted as it stands, too; `sparse` - True, or dict(max_bricks=, origin=) - fuses a
-    Gaussian model into one (tsdf.fuse_map's `sparse`)."""
+    Gaussian model into one (tsdf.fuse_map's `sparse`).  `volume_preview` - a view as mesh_render.view_tuple takes it -
+    writes the shaded ray cast of the VOLUME at that view (tsdf_raycast.raycast_frame, which takes `volume_preview_kw`;
+    z_far defaults to 10) as volume_preview.png next to mesh.ply: the surface the volume holds, before extraction, clean-up
+    and simplification touched it.  None adds no call."""
     from . import tsdf
     from .ply_io import write_mesh_ply
     if name is None:
@@ -336,6 +339,11 @@ def save_mesh(gaussians_or_volume, name, iteration=None, final: bool = True, cam
         from .mesh_render import render_mesh_frame
         from .viewer import save_frame
         save_frame(os.path.join(name, sub, "mesh_preview.png"), render_mesh_frame(verts, faces, preview))
+    if volume_preview is not None:
+        from .tsdf_raycast import raycast_frame
+        from .viewer import save_frame
+        save_frame(os.path.join(name, sub, "volume_preview.png"),
+                   raycast_frame(vol, volume_preview, **{"z_far": 10.0, **(volume_preview_kw or {})}))
     if topology:
         import json
         from .mesh_topology import mesh_topology

@@ -176,7 +176,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  alpha: float = 0.95, num_pixels: int = -1, keyframe_policy: Optional[KeyframePolicy] = None,
                  native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
                  stereo_matcher=None, second_order_exact: bool = False, viewer_every: int = 0,
-                 viewer_modes=("rgb",), viewer_follow: bool = True, mesh_volume=None, mesh_every: int = 1):
+                 viewer_modes=("rgb",), viewer_follow: bool = True, mesh_volume=None, mesh_every: int = 1,
+                 mesh_preview_every: int = 0, mesh_preview_kw=None):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -220,7 +221,10 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     frame's sensor depth with the camera's image when there is one (`sensor_depth`, a stereo matcher), else from the
     map's rendered view at the keyframe's pose (integrate_view) - which a dense box, sized from a finished map, cannot
     serve.  The result then also holds `mesh_keyframes`, the keyframes fused.  Tracking and mapping read nothing the
-    volume writes; None leaves the run as it is."""
+    volume writes; None leaves the run as it is.  `mesh_preview_every` = m > 0 (needs mesh_volume): after every m-th
+    keyframe fused, the volume is ray cast at that keyframe's tracked pose (tsdf_raycast.raycast_frame, which takes
+    `mesh_preview_kw`; z_far defaults to 10) - no mesh, no host read, so the stream does not stall - and the result
+    also holds `mesh_previews`: {frame id: uint8 [H,W,3] device tensor}.  0 adds no call."""
     if stereo_matcher is not None:
         if any(getattr(f, "image_right", None) is None for f in frames):
             raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
@@ -319,7 +323,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             raise RuntimeError("viewer: pair capacity still exceeded after growing the workspaces three times")
         view_frames[k] = shots
 
-    mesh_keyframes, n_keyframes = [], 0
+    mesh_keyframes, n_keyframes, mesh_previews = [], 0, {}
 
     def fuse_keyframe(k, fr):
         """Keyframe k into `mesh_volume` (every mesh_every-th one): outside the timed sections."""
@@ -335,6 +339,9 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         else:
             mesh_volume.integrate_view(gm, v, bg)
         mesh_keyframes.append(k)
+        if mesh_preview_every > 0 and (len(mesh_keyframes) - 1) % int(mesh_preview_every) == 0:
+            from .tsdf_raycast import raycast_frame
+            mesh_previews[k] = raycast_frame(mesh_volume, v, **{"z_far": 10.0, **(mesh_preview_kw or {})})
 
     t_track = t_map = 0.0
     n_track_iters = n_map_iters = n_map_views = 0
@@ -445,6 +452,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         result["view_frames"] = view_frames
     if mesh_volume is not None:
         result["mesh_keyframes"] = mesh_keyframes
+        if mesh_preview_every > 0:
+            result["mesh_previews"] = mesh_previews
     return result
 
 

@@ -317,6 +317,7 @@ class SparseTSDFVolume:
         self._alloc_scratch, self._alloc_key = None, None
         self._mesh_scratch, self._mesh_bricks = None, 0
         self._counts = torch.zeros(2, dtype=torch.int32, device=self.dev)
+        self.brick_epoch = 0      # calls that can change the brick list: tsdf_raycast.neighbor_table rebuilds on a change
 
     def reset(self):
         self.tsdf.fill_(1.0)
@@ -324,6 +325,7 @@ class SparseTSDFVolume:
         self.color.zero_()
         self.map_keys.fill_(-1)
         self.state.zero_()
+        self.brick_epoch += 1
 
     def stats(self) -> dict:
         """One host read: the counters, and the bytes the volume holds."""
@@ -411,6 +413,7 @@ class SparseTSDFVolume:
                 self._alloc_key = key
             a.scratch = self._alloc_scratch.data_ptr()
             _cabi.check(L.mgs_sparse_tsdf_allocate(C.byref(a), stream_ptr(self.dev)), "mgs_sparse_tsdf_allocate")
+            self.brick_epoch += 1
         # `keep` holds the converted inputs until the launches are enqueued; the allocator orders their reuse on this stream
         _cabi.check(L.mgs_sparse_tsdf_integrate(C.byref(a), stream_ptr(self.dev)), "mgs_sparse_tsdf_integrate")
         del keep
@@ -466,6 +469,16 @@ class SparseTSDFVolume:
             verts, faces, colors, _ = simplify_mesh(verts, faces, colors,
                                                     **simplify_keywords(simplify, self.voxel_size, self.origin))
         return verts, faces, colors
+
+    def raycast(self, T_w2c, fx, fy, cx, cy, H, W, **kw):
+        """tsdf_raycast.raycast of this volume: dict(depth, normal, color, hit_step) on the device, no host read."""
+        from .tsdf_raycast import raycast
+        return raycast(self, T_w2c, fx, fy, cx, cy, H, W, **kw)
+
+    def raycast_view(self, camera, **kw):
+        """tsdf_raycast.raycast_view of this volume at a camera object or a view tuple."""
+        from .tsdf_raycast import raycast_view
+        return raycast_view(self, camera, **kw)
 
     # ---- to and from dense planes (torch indexing; for tests and users, not on a hot path) ---------------------------
     def to_dense(self, lo=None, dims=None):
@@ -553,4 +566,5 @@ class SparseTSDFVolume:
         v = _cabi.SparseTsdfVolume()
         vol._volume(v)
         _cabi.check(_cabi.lib().mgs_sparse_tsdf_register(C.byref(v), 0, B, stream_ptr(dev)), "mgs_sparse_tsdf_register")
+        vol.brick_epoch += 1
         return vol

@@ -404,6 +404,18 @@ class TSDFVolume:
         return verts, faces, colors
 
 
+    # the methods of SparseTSDFVolume, one signature for both volumes
+    def raycast(self, T_w2c, fx, fy, cx, cy, H, W, **kw):
+        """tsdf_raycast.raycast of this volume: dict(depth, normal, color, hit_step) on the device, no host read."""
+        from .tsdf_raycast import raycast
+        return raycast(self, T_w2c, fx, fy, cx, cy, H, W, **kw)
+
+    def raycast_view(self, camera, **kw):
+        """tsdf_raycast.raycast_view of this volume at a camera object or a view tuple."""
+        from .tsdf_raycast import raycast_view
+        return raycast_view(self, camera, **kw)
+
+
 def sparse_volume(sparse, voxel_size: float, device, trunc=None, max_weight: float = 64.0):
     """The sparse_tsdf.SparseTSDFVolume that `sparse` - True, or dict(max_bricks=, origin=) - asks for."""
     from .sparse_tsdf import SparseTSDFVolume
