@@ -1750,6 +1750,113 @@ int32_t mgs_tsdf_raycast(const mgs_tsdf_raycast_args* args, void* stream);
 int32_t mgs_sparse_tsdf_raycast(const mgs_sparse_tsdf_raycast_args* args, void* stream);
 int32_t mgs_raycast_shade(const mgs_raycast_shade_args* args, void* stream);
 
+/* ---- frame-to-model ICP ("Frame-to-model ICP") ----------------------------------------------------------
+ * Point-to-plane alignment of a sensor depth plane against a model view (a ray cast's depth and camera-frame normals, or
+ * the surface planes of the viewer), the whole coarse-to-fine schedule enqueued at once, no host read.  The NumPy mirror
+ * icp.align_numpy (icp_rows_numpy, icp_solve_numpy) is the contract; the device equals it bit for bit and two runs give
+ * the same bytes: every fp32 and fp64 operation below is a single rounding and every sum is an integer sum.
+ *   Unknown   the rigid D [3,4] that takes sensor-camera to model-camera coordinates, fp64.  D_0 = T_model * T_init^-1
+ *             (rigid inverse and product below), the identity when T_init is NULL.
+ *   Rigid     inverse: R' = R^T, t'_a = -((R'_a0 t_0 + R'_a1 t_1) + R'_a2 t_2).  Product C = A B: C.R_ab = (A.R_a0 B.R_0b +
+ *             A.R_a1 B.R_1b) + A.R_a2 B.R_2b, C.t_a = ((A.R_a0 B.t_0 + A.R_a1 B.t_1) + A.R_a2 B.t_2) + A.t_a.  fp64.
+ *   Rows      (mgs k_icp_rows) over the sensor pixels u = 0 (mod stride), v = 0 (mod stride), in fp32, D rounded once to
+ *             fp32 (R, t), pixel centre 0 on both sides:
+ *             1 d = depth[v,u], n_s = normal[:,v,u].  INVALID unless d > 0, d finite, d <= depth_max and n_s != (0,0,0).
+ *             2 rx = (u - cx) / fx, ry = (v - cy) / fy; X = (rx d, ry d, d); p_a = ((R_a0 X_0 + R_a1 X_1) + R_a2 X_2) + t_a;
+ *               n'_a = (R_a0 n_s0 + R_a1 n_s1) + R_a2 n_s2.
+ *             3 RANGE unless p_2 > 0 and every |p_a| < 16.
+ *             4 u' = rintf(mfx (p_0 / p_2) + mcx), v' = rintf(mfy (p_1 / p_2) + mcy).  OUTSIDE unless |u'|, |v'| < 2^23
+ *               (in float, before the conversion to int: false for a NaN) and 0 <= u' < model_width, 0 <= v' <
+ *               model_height.  Nothing is loaded before this test.
+ *             5 d_m = model_depth[v',u'], n = model_normal at (v',u').  NO_MODEL unless d_m > 0, n != (0,0,0) and every
+ *               |n_a| <= 1 (false for a NaN: a unit normal passes, and the bound below needs it).
+ *             6 q = (((u' - mcx) / mfx) d_m, ((v' - mcy) / mfy) d_m, d_m), e = p - q.
+ *             7 DISTANCE unless (e_0^2 + e_1^2) + e_2^2 <= dist * dist; NORMAL unless (n_0 n'_0 + n_1 n'_1) + n_2 n'_2 >=
+ *               cos_min.
+ *             8 J = [n ; p x n] (translation first, the tau = [rho; theta] of mgs_pose_adam_args),
+ *               p x n = (p_1 n_2 - p_2 n_1, p_2 n_0 - p_0 n_2, p_0 n_1 - p_1 n_0); r = (n_0 e_0 + n_1 e_1) + n_2 e_2.
+ *             9 with w = [J r], the 28 products w_i w_j (i <= j, row-major) are one fp32 rounding each, and each enters
+ *               its sum as the int64 trunc(v * 2^30), exact in fp64.
+ *   Sums      28 int64 sums, the count of accepted pixels and one count per rejection (INVALID, RANGE, OUTSIDE,
+ *             NO_MODEL, DISTANCE, NORMAL): MGS_ICP_SUMS = 35 words, integer adds only, so any order gives the same bits.
+ *             Bound: |n_a| <= 1 and |p_a| < 16 give |J_i| < 2^5; dist <= 8 gives |r| <= sqrt(3) dist < 2^5; a product
+ *             is below 2^10, its fixed-point value below 2^40, and width * height <= 2^22 (else MGS_ERR_UNSUPPORTED)
+ *             keeps every sum below 2^62.  depth_max > 16 or dist > 8: MGS_ERR_BAD_ARGUMENT.
+ *   Solve     (k_icp_solve, one thread, fp64).  accepted < min_pixels: MGS_ICP_TOO_FEW.  H_ij = sum / 2^30 (i, j < 6),
+ *             g_i = sum_(i,6) / 2^30; H_ii += damping; m = max_i H_ii.  LDL^T by columns j: with t_k = L_jk d_k,
+ *             pivot_j = H_jj - sum_k<j L_jk t_k (k ascending); the pivot is tested BEFORE any division by it: if not
+ *             pivot_j > min_pivot_ratio * m the status is MGS_ICP_DEGENERATE, the column of L and d_j count as 0 and the
+ *             factorisation goes on so that all six pivots are recorded; else d_j = pivot_j and L_ij = (H_ij - sum_k<j
+ *             L_ik t_k) / d_j.  Then H x = -g: y_i = -g_i - sum_k<i L_ik y_k, z_i = y_i / d_i, x_i = z_i - sum_k>i L_ki
+ *             x_k (k ascending).
+ *   Update    s = (x_3^2 + x_4^2) + x_5^2, xx = x . x summed in index order.  Not s <= 0.25, or xx not finite:
+ *             MGS_ICP_STEP_TOO_LARGE.  a = sum_k (-s)^k / (2k+1)!, b = sum_k (-s)^k / (2k+2)!, c = sum_k (-s)^k / (2k+3)!
+ *             over k = 0 .. 6 by Horner's rule (MGS_ICP_EXP_TERMS: the first term left out is below one ulp of the
+ *             coefficient at s = 0.25; the derivation is in icp.hip).  With W = [theta]x and W2 = theta theta^T - s I:
+ *             R_E = (I + a W) + b W2, V = (I + b W) + c W2, t_E = V rho (summed as a rigid product's row), D <- E D.
+ *             xx < converged * converged ends the level (MGS_ICP_CONVERGED); the last iteration of the last level
+ *             otherwise ends with MGS_ICP_MAX_ITERATIONS.  A failure status leaves D and T_w2c as they were and ends
+ *             everything; the launches of a level that has converged, and all launches after a failure, return at once.
+ *   Outputs   T_w2c [4,4] f32 = D^-1 T_model (fp64, rounded once; written at the start and after every step), D [3,4]
+ *             f64, record [MGS_ICP_RECORD_WORDS] of 8-byte words: 0..27 sums, 28..34 counts (accepted, then the
+ *             rejections in the order above), 35..40 x (f64), 41..46 pivots (f64), 47 status, 48 level, 49 iteration
+ *             within the level, 50 iterations run, 51 the level that has converged (-1: none), of the last iteration
+ *             that ran.  The history, one row of MGS_ICP_HISTORY_WORDS words per enqueued iteration, lies in `scratch`
+ *             behind the partial sums, at byte mgs_icp_scratch_bytes(0): accepted, sum r^2 (fixed point), xx (f64),
+ *             status, ran (0 / 1), level, iteration, spare.
+ * Launches: one to start, then k_icp_rows (a persistent grid of at most MGS_ICP_ROWS_BLOCKS workgroups of 256, a wave per
+ * 8 x 8 tile of the stride grid, one plain store of a row of partial sums per workgroup, no atomics) and k_icp_solve per
+ * iteration.  `normal` is the plane mgs_depth_normal wrote with pixel_center = 0.
+ * A null struct or needed pointer, a side < 1, a focal length not > 0, num_levels outside 1 .. MGS_ICP_MAX_LEVELS, a
+ * stride or an iteration count < 1, more than MGS_ICP_MAX_ITERATIONS_TOTAL iterations, a layout flag outside {0, 1},
+ * dist, cos_min, depth_max, min_pivot_ratio, damping or converged that is NaN or negative (cos_min: outside [-1, 1]):
+ * MGS_ERR_BAD_ARGUMENT.  3 * model_width * model_height >= 2^31: MGS_ERR_UNSUPPORTED.  A refused call launches nothing. */
+#define MGS_ICP_ITERATING 0          /* the last iteration stepped; more were enqueued */
+#define MGS_ICP_CONVERGED 1
+#define MGS_ICP_MAX_ITERATIONS 2
+#define MGS_ICP_TOO_FEW 3
+#define MGS_ICP_DEGENERATE 4
+#define MGS_ICP_STEP_TOO_LARGE 5
+#define MGS_ICP_MAX_LEVELS 8
+#define MGS_ICP_MAX_ITERATIONS_TOTAL 1024
+#define MGS_ICP_SUMS 35
+#define MGS_ICP_RECORD_WORDS 56
+#define MGS_ICP_HISTORY_WORDS 8
+#define MGS_ICP_ROWS_BLOCKS 256
+#define MGS_ICP_EXP_TERMS 7
+#define MGS_ICP_MAX_PIXELS (1 << 22)
+
+typedef struct mgs_icp_args {
+  int32_t width, height;                 /* the sensor planes; width * height <= 2^22 */
+  int32_t model_width, model_height;
+  int32_t model_normal_chw;              /* 0: model_normal is [H,W,3] (the ray cast), 1: [3,H,W] (mgs_depth_normal) */
+  int32_t num_levels;
+  int32_t min_pixels;
+  int32_t reserved0;
+  int32_t stride[MGS_ICP_MAX_LEVELS];
+  int32_t iterations[MGS_ICP_MAX_LEVELS];
+  float fx, fy, cx, cy;                  /* sensor */
+  float mfx, mfy, mcx, mcy;              /* model */
+  float dist, cos_min, depth_max;
+  float reserved1;
+  double min_pivot_ratio, damping, converged;
+  const float* depth;                    /* [H,W] sensor */
+  const float* normal;                   /* [3,H,W] sensor */
+  const float* model_depth;              /* [Hm,Wm] */
+  const float* model_normal;
+  const float* T_model;                  /* [4,4] world -> model camera */
+  const float* T_init;                   /* [4,4] world -> sensor camera at the start, or NULL (= T_model) */
+  void* scratch;                         /* mgs_icp_scratch_bytes(total iterations), 8-byte aligned */
+  float* T_w2c;                          /* [4,4] out */
+  double* D;                             /* [3,4] out */
+  int64_t* record;                       /* [MGS_ICP_RECORD_WORDS] out */
+} mgs_icp_args;
+
+int32_t mgs_icp_args_size(void);   /* sizeof(mgs_icp_args): the binding checks its mirror against it when the library loads;
+                                      the struct is not in mgs_struct_size()'s numbered list, which ends where it ended */
+uint64_t mgs_icp_scratch_bytes(int32_t max_iterations_total);   /* 0 for a count outside 0 .. 1024 */
+int32_t mgs_icp_align(const mgs_icp_args* args, void* stream);
+
 /* ---- mesh clean-up ("Mesh clean-up") -------------------------------------------------------------------
  * Connected components of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL),
  * clusters kept by size, vertices / colours / faces compacted.  The NumPy mirror mesh_clean.clean_mesh_numpy is the

@@ -50,6 +50,7 @@ EXPORTS = (
     "mgs_sparse_tsdf_mesh_count", "mgs_sparse_tsdf_mesh_emit",
     "mgs_tsdf_raycast_args_size", "mgs_sparse_tsdf_raycast_args_size", "mgs_raycast_shade_args_size",
     "mgs_sparse_tsdf_raycast_scratch_bytes", "mgs_tsdf_raycast", "mgs_sparse_tsdf_raycast", "mgs_raycast_shade",
+    "mgs_icp_args_size", "mgs_icp_scratch_bytes", "mgs_icp_align",
     "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
     "mgs_mesh_components",
     "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
@@ -458,6 +459,23 @@ class RaycastShadeArgs(C.Structure):
                 + [(n, _fp) for n in ("depth", "normal", "color", "hit_step", "lut", "out")])
 
 
+# MGS_ICP_*: the statuses, then the sizes
+ICP_ITERATING, ICP_CONVERGED, ICP_MAX_ITERATIONS, ICP_TOO_FEW, ICP_DEGENERATE, ICP_STEP_TOO_LARGE = range(6)
+ICP_MAX_LEVELS, ICP_MAX_ITERATIONS_TOTAL, ICP_SUMS, ICP_RECORD_WORDS, ICP_HISTORY_WORDS = 8, 1024, 35, 56, 8
+ICP_ROWS_BLOCKS, ICP_EXP_TERMS, ICP_MAX_PIXELS = 256, 7, 1 << 22
+
+
+class IcpArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "model_width", "model_height", "model_normal_chw", "num_levels",
+                                          "min_pixels", "reserved0")]
+                + [("stride", C.c_int32 * ICP_MAX_LEVELS), ("iterations", C.c_int32 * ICP_MAX_LEVELS)]
+                + [(n, C.c_float) for n in ("fx", "fy", "cx", "cy", "mfx", "mfy", "mcx", "mcy", "dist", "cos_min", "depth_max",
+                                            "reserved1")]
+                + [(n, C.c_double) for n in ("min_pivot_ratio", "damping", "converged")]
+                + [(n, _fp) for n in ("depth", "normal", "model_depth", "model_normal", "T_model", "T_init", "scratch", "T_w2c",
+                                      "D", "record")])
+
+
 MESH_CLEAN_MAX_ITEMS = (2 ** 31 - 1) // 3     # 3 V, 3 F < 2^31: 32-bit element indices of the [n,3] arrays
 MESH_CLEAN_COUNTS = 5                         # V', F', clusters, kept clusters, bad faces
 
@@ -788,6 +806,11 @@ def lib():
         fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
     L.mgs_sparse_tsdf_raycast_scratch_bytes.restype = C.c_uint64
     L.mgs_sparse_tsdf_raycast_scratch_bytes.argtypes = [C.c_int32]
+    L.mgs_icp_args_size.restype, L.mgs_icp_args_size.argtypes = C.c_int32, []
+    if L.mgs_icp_args_size() != C.sizeof(IcpArgs):
+        raise NativeLibraryError("IcpArgs does not have the size of mgs_icp_args")
+    L.mgs_icp_scratch_bytes.restype, L.mgs_icp_scratch_bytes.argtypes = C.c_uint64, [C.c_int32]
+    L.mgs_icp_align.restype, L.mgs_icp_align.argtypes = C.c_int32, [C.POINTER(IcpArgs), C.c_void_p]
     L.mgs_mesh_clean_args_size.restype, L.mgs_mesh_clean_args_size.argtypes = C.c_int32, []
     if L.mgs_mesh_clean_args_size() != C.sizeof(MeshCleanArgs):
         raise NativeLibraryError("MeshCleanArgs does not have the size of mgs_mesh_clean_args")

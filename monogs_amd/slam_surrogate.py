@@ -177,7 +177,7 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
                  native_keyframe_seed: bool = False, native_frame_prepare: bool = False, track_on_edges: bool = False,
                  stereo_matcher=None, second_order_exact: bool = False, viewer_every: int = 0,
                  viewer_modes=("rgb",), viewer_follow: bool = True, mesh_volume=None, mesh_every: int = 1,
-                 mesh_preview_every: int = 0, mesh_preview_kw=None):
+                 mesh_preview_every: int = 0, mesh_preview_kw=None, icp_init: bool = False, icp_kw=None):
     """Tracking + mapping over `frames`; returns a dict with the estimated poses, timings and the
     final map.  `sensor_depth`: insert keyframes from the frames' depth (RGB-D initialisation) instead
     of the monocular prior / rendered depth.  `rgbd_tracking` (needs sensor_depth): track every frame with
@@ -224,7 +224,17 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     volume writes; None leaves the run as it is.  `mesh_preview_every` = m > 0 (needs mesh_volume): after every m-th
     keyframe fused, the volume is ray cast at that keyframe's tracked pose (tsdf_raycast.raycast_frame, which takes
     `mesh_preview_kw`; z_far defaults to 10) - no mesh, no host read, so the stream does not stall - and the result
-    also holds `mesh_previews`: {frame id: uint8 [H,W,3] device tensor}.  0 adds no call."""
+    also holds `mesh_previews`: {frame id: uint8 [H,W,3] device tensor}.  0 adds no call.
+    `icp_init` (needs mesh_volume and a sensor or stereo depth): every tracked frame, once the volume holds a keyframe,
+    first ray casts the volume at the previous frame's pose and aligns the frame's depth to it (icp.track_against_volume,
+    which takes `icp_kw`); the tracker's camera starts from the ICP pose when its status is converged or out of
+    iterations, else from the previous pose as without it - chosen on the device by the status word, no host read, inside
+    the timed tracking section.  The result then also holds `icp_records`: {frame id: icp.read_record's dict}, read once
+    after the run.  False makes no ICP or ray-cast call."""
+    if icp_init and (mesh_volume is None or not (sensor_depth or stereo_matcher is not None)):
+        raise ValueError("icp_init needs mesh_volume and a sensor or stereo depth (sensor_depth=True or a stereo_matcher)")
+    if icp_init and stereo_matcher is None and any(f.depth is None for f in frames):
+        raise ValueError("icp_init needs a depth image in every frame")
     if stereo_matcher is not None:
         if any(getattr(f, "image_right", None) is None for f in frames):
             raise ValueError("stereo_matcher needs image_right in every frame (load_sequence(stereo_baseline=...))")
@@ -343,6 +353,16 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
             from .tsdf_raycast import raycast_frame
             mesh_previews[k] = raycast_frame(mesh_volume, v, **{"z_far": 10.0, **(mesh_preview_kw or {})})
 
+    icp_raw = {}
+
+    def icp_start(k, fr, vp, T_prev):
+        """vp.T <- the ICP pose of the frame against the volume's ray cast at T_prev, if its status is ok (on the device)."""
+        from . import icp as _icp
+        res = _icp.track_against_volume(mesh_volume, depth_of(fr), T_prev, vp, read=False, **(icp_kw or {}))
+        with torch.no_grad():
+            vp.T.copy_(_icp.select_pose(res, vp.T))
+        icp_raw[k] = res["record"]
+
     t_track = t_map = 0.0
     n_track_iters = n_map_iters = n_map_views = 0
     cams = {}
@@ -370,6 +390,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         t0 = time.perf_counter()
         if preparer is not None:                                  # the frame's preparation is part of its tracking time
             vp = camera(fr, cams[k - 1].T.detach().clone())
+        if icp_init and mesh_keyframes:
+            icp_start(k, fr, vp, cams[k - 1].T.detach())
         trk = NativeTracker(vp, gm, bg, gt_depth=depth_of(fr) if rgbd_tracking else None, alpha=alpha,
                             num_pixels=num_pixels, sample_seed=seed + k,
                             mask=vp.rgb_pixel_mask if track_on_edges else None)
@@ -454,6 +476,10 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
         result["mesh_keyframes"] = mesh_keyframes
         if mesh_preview_every > 0:
             result["mesh_previews"] = mesh_previews
+    if icp_init:
+        from .icp import read_record
+        words = torch.stack([icp_raw[k] for k in sorted(icp_raw)]).cpu().numpy() if icp_raw else []
+        result["icp_records"] = {k: read_record(w) for k, w in zip(sorted(icp_raw), words)}
     return result
 
 

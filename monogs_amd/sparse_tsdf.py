@@ -480,6 +480,11 @@ class SparseTSDFVolume:
         from .tsdf_raycast import raycast_view
         return raycast_view(self, camera, **kw)
 
+    def track(self, depth, T_prev, view, **kw):
+        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it."""
+        from .icp import track_against_volume
+        return track_against_volume(self, depth, T_prev, view, **kw)
+
     # ---- to and from dense planes (torch indexing; for tests and users, not on a hot path) ---------------------------
     def to_dense(self, lo=None, dims=None):
         """(origin, tsdf, weight [nz,ny,nx], color [3,nz,ny,nx]) of the box of `dims` = (nx, ny, nz) points whose first

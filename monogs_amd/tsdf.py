@@ -415,6 +415,11 @@ class TSDFVolume:
         from .tsdf_raycast import raycast_view
         return raycast_view(self, camera, **kw)
 
+    def track(self, depth, T_prev, view, **kw):
+        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it."""
+        from .icp import track_against_volume
+        return track_against_volume(self, depth, T_prev, view, **kw)
+
 
 def sparse_volume(sparse, voxel_size: float, device, trunc=None, max_weight: float = 64.0):
     """The sparse_tsdf.SparseTSDFVolume that `sparse` - True, or dict(max_bricks=, origin=) - asks for."""
