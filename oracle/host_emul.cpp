@@ -27,6 +27,7 @@ namespace {
 
 struct Ctx {
   Camera cam;
+  int clamp_grad_upstream = 1;                // backward's treatment of the field-of-view clamp (raster_math.h)
   int N = 0;
   std::vector<SplatRec> rec;
   std::vector<int32_t> tile_offset;           // [T+1]
@@ -58,6 +59,14 @@ extern "C" {
 void* emul_create() { return new Ctx(); }
 void emul_destroy(void* h) { delete (Ctx*)h; }
 
+// 1 = the clamped t.x is a constant of z (the product default), 0 = the exact derivative of the clamp; holds for
+// every later emul_backward on this handle.
+void emul_set_clamp_gradient(void* h, int upstream) {
+  Ctx& c = *(Ctx*)h;
+  c.clamp_grad_upstream = upstream ? 1 : 0;
+  c.cam.clamp_grad_upstream = c.clamp_grad_upstream;
+}
+
 // exact_cull = 0 reproduces the reference's bounding-square binning; 1 applies the
 // product's exact tile culling (results must be identical, pair count smaller).
 int64_t emul_forward(void* h, int N, int W, int H, float tanfovx, float tanfovy,
@@ -70,6 +79,7 @@ int64_t emul_forward(void* h, int N, int W, int H, float tanfovx, float tanfovy,
   Ctx& c = *(Ctx*)h;
   c.cam = make_camera(V, PM, Praw, campos, W, H, tanfovx, tanfovy, scale_modifier, sh_degree,
                       sh_coeffs);
+  c.cam.clamp_grad_upstream = c.clamp_grad_upstream;
   c.N = N;
   c.rec.resize(N);
   const Camera& cam = c.cam;

@@ -36,6 +36,7 @@ def lib():
         _lib.emul_num_threads.restype = C.c_int
         _lib.emul_destroy.argtypes = [C.c_void_p]
         _lib.emul_forward.restype = C.c_int64
+        _lib.emul_set_clamp_gradient.argtypes = [C.c_void_p, C.c_int]
     return _lib
 
 
@@ -51,6 +52,10 @@ class HostEmul:
 
     def __init__(self):
         self.h = C.c_void_p(lib().emul_create())
+
+    def set_clamp_gradient_mode(self, mode: str) -> None:
+        """"upstream" (the default) or "exact": the backward's treatment of the field-of-view clamp."""
+        lib().emul_set_clamp_gradient(self.h, {"upstream": 1, "exact": 0}[mode])
 
     @staticmethod
     def num_threads() -> int:

@@ -10,7 +10,14 @@ import torch
 import raster_parity as P
 
 
-ALL_NAMES = P.CASE_NAMES + [P.LONG]
+ALL_NAMES = P.CASE_NAMES + [P.LONG] + P.DECISION_NAMES
+DECISIONS = "decisions_70x45"
+
+
+def _modes(name):
+    """The decision scene is held under both treatments of the clamp in the backward, every other scene under the
+    product default."""
+    return ("upstream", "exact") if name == DECISIONS else ("upstream",)
 
 
 def _caps(ref):
@@ -22,16 +29,18 @@ def _caps(ref):
 @pytest.mark.parametrize("name", ALL_NAMES)
 def test_reference_alone_stays_within_bounds(name):
     """scene_margins (inside reference()) and the caps hold, and the fp32 oracle passes against the fp64 one."""
-    ref = P.reference(name)
-    shares = _caps(ref)
-    stats = P.assert_parity(P.run_oracle(ref.case, torch.float32), ref, "fp32 oracle")
-    print(name, "caps:", f"pixels {100 * shares['pixels']:.2f} %, radii {100 * shares['radii']:.2f} %, rows",
-          ", ".join(f"{k} {100 * v:.1f} %" for k, v in shares["rows"].items()), "| fp32 oracle,", P.ratios(stats))
+    for mode in _modes(name):
+        ref = P.reference(name, mode)
+        shares = _caps(ref)
+        stats = P.assert_parity(P.run_oracle(ref.case, torch.float32, clamp_grad=mode), ref, f"fp32 oracle, {mode}")
+        print(name, mode, "caps:", f"pixels {100 * shares['pixels']:.2f} %, radii {100 * shares['radii']:.2f} %, rows",
+              ", ".join(f"{k} {100 * v:.1f} %" for k, v in shares["rows"].items()), "| fp32 oracle,", P.ratios(stats))
 
 
-def _emulate(c, exact_cull):
+def _emulate(c, exact_cull, clamp_grad="upstream"):
     from oracle.host_emul import HostEmul
     em = HostEmul()
+    em.set_clamp_gradient_mode(clamp_grad)
     img, radii, dep, opa, nt = em.forward(P.settings_of(c, torch.float32), c.m, c.sh, c.col, c.o, c.s, c.r, c.cov,
                                           exact_cull=exact_cull)
     HW = c.cam.H * c.cam.W
@@ -46,11 +55,14 @@ def _emulate(c, exact_cull):
 def test_host_emulation_stays_within_bounds(built, name):
     """Forward with the reference's bounding-square binning and with the exact cull (box_reachable: "never rejects a
     contributing pair" - checked pixel by pixel, on the grazing scenes in particular), and the backward of each."""
-    ref = P.reference(name)
-    for exact in (False, True):
-        got, _ = _emulate(ref.case, exact)
-        stats = P.assert_parity(got, ref, f"host emulation, exact_cull={exact}")
-        print(name, "exact_cull", exact, P.ratios(stats))
+    for mode in _modes(name):
+        ref = P.reference(name, mode)
+        for exact in (False, True):
+            got, pairs = _emulate(ref.case, exact, mode)
+            stats = P.assert_parity(got, ref, f"host emulation, exact_cull={exact}, {mode}")
+            print(name, mode, "exact_cull", exact, P.ratios(stats))
+            if name in P.TIE_NAMES:          # the cull drops nothing either: the tile's list is the whole scene
+                assert pairs == ref.case.m.shape[0], pairs
 
 
 @pytest.mark.parametrize("name", ["grazing_41x23", "grazing_49x33", "grazing_long"])
@@ -231,3 +243,186 @@ def test_mutants_are_rejected_here_and_accepted_by_the_aggregate_thresholds():
             print("    " + line)
         assert not stats["ok"], f"mutant '{name}' passes the per-pixel / per-row comparison"
         assert old == accepted, f"mutant '{name}': aggregate thresholds {'accept' if old else 'reject'} it"
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# decision scenes: what they are, from the reference alone, and the mutants they must reject
+# ---------------------------------------------------------------------------------------------------------------------
+# rows of decisions_70x45 (raster_parity._decisions): per group the order is +2 band, -2 band, +16 band, -16 band
+NEAR = dict(visible=[0, 2, 6], culled=[1, 3, 4, 5, 7])              # 0.2 (1 +- 2 band), 0.2 (1 +- 16 band), 0.1, 0.19, 0.21, behind
+CLAMP_FIRST, RECT_FIRST = 8, 24
+CLAMPED = [CLAMP_FIRST + 4 * side + j for side in range(4) for j in (0, 2)]       # beyond the limit: + 2 band, + 16 band
+CLAMP_PLUS2 = [CLAMP_FIRST + 4 * side for side in range(4)]
+CLAMP_MINUS2 = [CLAMP_FIRST + 4 * side + 1 for side in range(4)]
+
+
+def test_decision_scene_sits_where_it_claims():
+    """Nothing is taken out of it, every Gaussian of a group lies 2 or 16 bands from its decision and on the side it
+    is meant to, the rectangle splats end 0.5 px before / after their tile boundary with the oracle's own radius, the
+    visible ones come out with radii > 0 and full gradient rows, the others with radii 0 and zero rows."""
+    built = P._BUILDERS[DECISIONS]()
+    ref = P.reference(DECISIONS)
+    c, out, K, band = ref.case, ref.out, P.O.CONSTANTS, P.CONST["band"]
+    assert c.m.shape[0] == built.m.shape[0] == 32 and torch.equal(c.m, built.m)
+    trips, _ = P.margin_trips(c, out, ref.radius_fragile)
+    assert not any(m.any() for m in trips.values()) and not ref.radius_fragile.any()
+    m = c.m.double()
+    z = m[:, 2]
+    steps = torch.tensor([2.0, -2.0, 16.0, -16.0], dtype=torch.float64) * band
+    assert torch.allclose(z[:4] / K["near_z"] - 1.0, steps, rtol=1e-3, atol=0)
+    assert z[4:8].tolist() == pytest.approx([0.1, 0.19, 0.21, -1.0])
+    for side, (axis, sign, tanfov) in enumerate(((0, 1, c.cam.tanfovx), (0, -1, c.cam.tanfovx), (1, 1, c.cam.tanfovy), (1, -1, c.cam.tanfovy))):
+        i = CLAMP_FIRST + 4 * side
+        ratio = sign * m[i:i + 4, axis] / z[i:i + 4] / (K["fov_clamp"] * tanfov)
+        assert torch.allclose(ratio - 1.0, steps, rtol=1e-3, atol=0), (side, ratio)
+        assert ((2.0 <= z[i:i + 4]) & (z[i:i + 4] <= 3.0)).all()
+    # depths are distinct and well separated: the closest two are the near-plane pair at 0.2 (1 +- 2 band), 4 bands
+    # = 2.7e-3 apart, against the 1e-6 below which the order inside a tile would be in question
+    zs = torch.sort(z[z > 0]).values
+    assert ((zs[1:] - zs[:-1]) / zs[1:]).min() > 3.9 * band > 1000 * P.DEPTH_GAP
+    # the rectangle splats, with the radius the oracle would give them were they visible
+    pr = out["info"]["proj"]
+    rad = torch.ceil(K["radius_sigma"] * torch.sqrt(P._lambda_max(pr.cov2d.detach())))
+    xy = pr.xy.detach()
+    gx, gy = (c.cam.W + 15) // 16, (c.cam.H + 15) // 16
+    ends = []
+    for j, (axis, side, edge) in enumerate(((0, 1, 1.0), (0, -1, 16.0 * gx), (1, 1, 1.0), (1, -1, 16.0 * gy))):
+        for k in (0, 1):
+            i = RECT_FIRST + 2 * j + k
+            ends.append(side * (xy[i, axis] + side * rad[i] - edge))
+    assert torch.allclose(torch.stack(ends), torch.tensor([-0.5, 0.5] * 4, dtype=torch.float64), atol=1e-4), ends
+    visible = NEAR["visible"] + list(range(CLAMP_FIRST, RECT_FIRST)) + [RECT_FIRST + 2 * j + 1 for j in range(4)]
+    assert (out["radii"] > 0).nonzero().flatten().tolist() == sorted(visible)
+    # a visible splat that reaches a pixel has a full row in every tensor, a culled one a zero row
+    reaches = out["n_touched"] > 0
+    assert reaches[NEAR["visible"]].all() and reaches[CLAMP_FIRST:RECT_FIRST].all()
+    for mode in ("upstream", "exact"):
+        g = P.reference(DECISIONS, mode).out["grads"]
+        for name, rows in g.items():
+            n = rows.norm(dim=1)
+            assert (n[reaches] > 0).all(), (mode, name)
+            assert (n[out["radii"] == 0] == 0).all(), (mode, name)
+            used = rows[:, :2] if name == "means2D" else rows        # the third column of means2D is never written
+            assert (used[reaches] != 0).all(), (mode, name)
+
+
+@pytest.mark.parametrize("name", P.TIE_NAMES)
+def test_tie_scenes_are_what_they_claim(name):
+    """Most sorted neighbours are exact ties; every pair of the tile is well above 1/255 (raw alpha >= 1.15/255), so the
+    list holds all N splats, past the sort class the scene is for; ties_40 and ties_1100 end at T >= 10 t_stop, ties_4200
+    stops everywhere and no pixel's allowance exceeds its base."""
+    ref = P.reference(name)
+    c, out, K = ref.case, ref.out, P.O.CONSTANTS
+    N = c.m.shape[0]
+    assert N == P._BUILDERS[name]().m.shape[0] and N > P.TIE_LIST_CLASS[name]
+    assert torch.equal(c.cam.viewmatrix, torch.eye(4)) and (c.cam.W, c.cam.H) == (16, 16)
+    depth = out["info"]["proj"].depth.detach()
+    assert torch.equal(depth, c.m[:, 2].double()) and torch.equal(depth * 8, torch.round(depth * 8))
+    d = torch.sort(depth).values
+    assert (d[1:] == d[:-1]).sum() > 0.6 * (N - 1)
+    assert out["info"]["pairs"] == N
+    seen = {}
+    with P.hooks(pairs=lambda tx, ty, ids, raw, inc: seen.update(raw=raw, ids=ids)):
+        P.run_oracle(c, backward=False)
+    assert seen["ids"].numel() == N and seen["raw"].min() >= 1.15 / 255 and seen["raw"].max() <= 2.5 / 255
+    final_T = 1.0 - out["opacity"]
+    if name == P.STOPS:
+        assert final_T.max() < 1.02 * K["t_stop"]
+        a, k = ref.allow, P.CONST
+        assert not ((a["image"] > k["base"]) | (a["depth"] > k["base_depth"]) | (a["opacity"] > k["base"])).any()
+    else:
+        assert final_T.min() >= P.MIN_FINAL_T * K["t_stop"], final_T.min()
+    P.check_caps(ref)
+
+
+def _over(stats):
+    return stats["over"]
+
+
+def test_a_moved_near_plane_is_rejected():
+    """near_z x (1 +- 4 band): the splat at 0.2 (1 + 2 band) resp. 0.2 (1 - 2 band) changes sides - its radius differs, its
+    rows are over and so are more than 100 of the pixels it owns."""
+    ref = P.reference(DECISIONS)
+    band = P.CONST["band"]
+    for factor, row in ((1 + 4 * band, 0), (1 - 4 * band, 1)):
+        with P.thresholds(near_z=factor):
+            mut = P.run_oracle(ref.case)
+        stats = P.assert_parity(mut, ref, raise_on_fail=False)
+        o = _over(stats)
+        print(f"near_z x {factor:.5f}:", o)
+        assert not stats["ok"] and o["radii"] == [row]
+        assert o["pixels"]["image"] > 100 and o["pixels"]["opacity"] > 100
+        assert all(row in rows for rows in o["rows"].values())
+
+
+def test_a_moved_clamp_limit_is_rejected():
+    """fov_clamp x (1 +- 4 band), under both backward treatments: the four splats at 1.3 tanfov (1 + 2 band) resp.
+    (1 - 2 band) change their clamp flag, and the means3D row of each of them is over.  (The limit enters the forward
+    of every clamped splat too, so pixels and a row or two of the other splats are over as well.)"""
+    band = P.CONST["band"]
+    for mode in ("upstream", "exact"):
+        ref = P.reference(DECISIONS, mode)
+        for factor, flipped in ((1 + 4 * band, CLAMP_PLUS2), (1 - 4 * band, CLAMP_MINUS2)):
+            with P.thresholds(fov_clamp=factor):
+                mut = P.run_oracle(ref.case, clamp_grad=mode)
+            stats = P.assert_parity(mut, ref, raise_on_fail=False)
+            print(f"fov_clamp x {factor:.5f}, {mode}:", _over(stats))
+            assert not stats["ok"] and not _over(stats)["radii"]
+            assert set(flipped) <= set(_over(stats)["rows"]["means3D"])
+
+
+def test_the_other_clamp_gradient_treatment_is_rejected():
+    """"exact" against the "upstream" reference and the reverse: the forward is the same, so no pixel and no radius
+    moves; the means3D rows of all eight clamped splats are over and no other row of any tensor.  (dtau, which sums
+    the same camera-space gradients, is over too.)"""
+    up, ex = P.reference(DECISIONS, "upstream"), P.reference(DECISIONS, "exact")
+    for got, ref in ((ex.out, up), (up.out, ex)):
+        stats = P.assert_parity(got, ref, raise_on_fail=False)
+        o = _over(stats)
+        print(o, P.ratios(stats))
+        assert not stats["ok"] and not o["radii"] and not any(o["pixels"].values())
+        assert o["rows"].pop("means3D") == CLAMPED
+        assert not any(o["rows"].values())
+
+
+def _by_descending_index(depth):
+    def order(tx, ty, ids):
+        d, i = depth[ids].tolist(), ids.tolist()
+        return ids[torch.tensor(sorted(range(len(i)), key=lambda k: (d[k], -i[k])))]
+    return order
+
+
+@pytest.mark.parametrize("name", P.TIE_NAMES)
+def test_ties_broken_by_descending_index_are_rejected(name):
+    ref = P.reference(name)
+    with P.hooks(order=_by_descending_index(ref.out["info"]["proj"].depth.detach())):
+        mut = P.run_oracle(ref.case)
+    stats = P.assert_parity(mut, ref, raise_on_fail=False)
+    print(name, {k: (v if k != "rows" else {t: len(r) for t, r in v.items()}) for k, v in _over(stats).items()})
+    assert not stats["ok"] and _over(stats)["pixels"]["image"] == 256
+
+
+def test_one_exchanged_pair_of_tied_neighbours_is_rejected_by_its_rows():
+    """ties_1100, the first tied neighbours from the middle of the list on: the image moves by less than `base` (no
+    pixel is over), the two splats' gradient rows catch it."""
+    ref = P.reference("ties_1100")
+    depth = ref.out["info"]["proj"].depth.detach()
+    order = torch.sort(depth, stable=True).indices
+    d = depth[order]
+    tied = (d[1:] == d[:-1]).nonzero().flatten()
+    pos = int(tied[tied >= d.numel() // 2][0])
+    pair = sorted((int(order[pos]), int(order[pos + 1])))
+
+    def swap(tx, ty, ids):
+        ids = ids.clone()
+        ids[pos], ids[pos + 1] = int(ids[pos + 1]), int(ids[pos])
+        return ids
+
+    with P.hooks(order=swap):
+        mut = P.run_oracle(ref.case)
+    assert not torch.equal(mut["image"], ref.out["image"])
+    stats = P.assert_parity(mut, ref, raise_on_fail=False)
+    o = _over(stats)
+    print("exchanged", pair, "at list position", pos, o, P.ratios(stats))
+    assert not stats["ok"] and not any(o["pixels"].values())
+    assert o["rows"]["colors"] == pair and o["rows"]["means3D"] == pair

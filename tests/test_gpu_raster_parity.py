@@ -1,6 +1,7 @@
 """The HIP rasteriser held to the fp64 oracle pixel by pixel and Gaussian row by row, with the oracle's own flip
-allowance (tests/raster_parity.py; DESIGN.md section 2, "How parity is held").  The scenes are small - the largest is
-1468 splats at 150x101 - and the three fp64 oracle runs of a scene dominate a test's time."""
+allowance (tests/raster_parity.py; DESIGN.md section 2, "How parity is held").  The scenes are small - the largest are
+1468 splats at 150x101 and 4200 splats in one 16x16 tile - and the three fp64 oracle runs of a scene dominate a test's
+time."""
 import pytest
 import torch
 
@@ -49,23 +50,44 @@ def _identical(a, b):
     assert (a["tau"] is None and b["tau"] is None) or torch.equal(a["tau"], b["tau"])
 
 
-@pytest.mark.parametrize("name", P.CASE_NAMES + [P.LONG])
+@pytest.mark.parametrize("name", P.CASE_NAMES + [P.LONG] + P.DECISION_NAMES)
 def test_rasteriser_matches_the_fp64_oracle_per_pixel_and_per_row(built, name):
-    """The last case is the scene of long oblique needles (sigma up to 50 px at 30 / 45 / 60 degrees, blended): the
+    """The case grazing_long is the scene of long oblique needles (sigma up to 50 px at 30 / 45 / 60 degrees, blended): the
     per-quadrant box test, the polynomial exponent and the backward's reach words on the splats where the cross term
     of the conic matters most.  Its conic cancels in fp32, so it is held to constants measured on that scene alone
     (raster_parity.CONST_LONG) and its cap shares are not asserted; a pair dropped up to 5 % above 1/255 in any whole
-    tile of it still fails (tests/test_cpu_raster_parity.py)."""
-    ref = P.reference(name)              # asserts the scene's margins
-    if name != P.LONG:
-        P.check_caps(ref)
-    stats = P.assert_parity(_run(ref.case), ref, "HIP rasteriser")
-    print(name, P.ratios(stats))
+    tile of it still fails (tests/test_cpu_raster_parity.py).
+    The decision scenes put Gaussians 2 and 16 bands on either side of the near plane, the field-of-view clamp and the
+    first tile boundary in play (decisions_70x45, under both treatments of the clamp in the backward), and exact depth
+    ties into one tile's list of 40, 1100 and 4200 splats: the register network, the LDS class and the in-HBM class of
+    the tile sort, and the reverse walk of the same lists in the backward."""
+    from monogs_amd import rasterizer as R
+    modes = ("upstream", "exact") if name == "decisions_70x45" else ("upstream",)
+    assert R._clamp_gradient_mode == R.CLAMP_GRADIENT_MODES["upstream"]      # the product default
+    try:
+        for mode in modes:
+            ref = P.reference(name, mode)              # asserts the scene's margins
+            if name != P.LONG:
+                P.check_caps(ref)
+            R.set_clamp_gradient_mode(mode)
+            stats = P.assert_parity(_run(ref.case), ref, f"HIP rasteriser, clamp gradient {mode}")
+            print(name, mode, P.ratios(stats))
+            if name in P.TIE_NAMES:      # one tile, nothing culled: its list is the whole scene, past the sort class
+                assert R.last_stats["pairs"] == ref.case.m.shape[0] > P.TIE_LIST_CLASS[name], R.last_stats
+    finally:
+        R.set_clamp_gradient_mode("upstream")
 
 
 def test_saturation_scene_is_bit_identical_run_to_run(built):
     """The gradient path is atomic-free with a fixed summation order: two runs agree in every bit."""
     c = P.case("saturation")
+    _identical(_run(c), _run(c))
+
+
+def test_longest_tie_scene_is_bit_identical_run_to_run(built):
+    """4200 splats at 32 depths in one tile: the in-HBM sort decides every tie by the Gaussian index, so the list, the
+    blend and the reverse walk agree in every bit."""
+    c = P.case("ties_4200")
     _identical(_run(c), _run(c))
 
 
