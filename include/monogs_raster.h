@@ -1857,6 +1857,84 @@ int32_t mgs_icp_args_size(void);   /* sizeof(mgs_icp_args): the binding checks i
 uint64_t mgs_icp_scratch_bytes(int32_t max_iterations_total);   /* 0 for a count outside 0 .. 1024 */
 int32_t mgs_icp_align(const mgs_icp_args* args, void* stream);
 
+/* ---- RGB-D alignment: photometric rows in the ICP ("RGB-D alignment") ------------------------------------
+ * The combined cost E = sum r_geo^2 + lambda^2 sum r_I^2, r_I = I_model(pi(D p)) - I_sensor(u), lambda = photo_weight.
+ * On a textured plane the photometric rows carry the three directions [n ; p x n] cannot see.  The mirror is
+ * icp.align_numpy(image=, photo_weight=) (intensity_planes_torch, icp_rows_numpy(photo=)); the device equals it bit for
+ * bit.  mgs_icp_align and everything above are untouched by this entry.
+ *   Intensity (k_icp_intensity, one launch per image, a thread per pixel).  rgb is [H,W,3] (chw = 0, the ray cast's
+ *             colour) or [3,H,W] (chw = 1, a camera's image); `valid` is NULL or an fp32 plane [H,W] that is on where its
+ *             value is > 0 (false for a NaN; the model passes the ray cast's depth).  A pixel is VALID iff it lies in the
+ *             image, every channel c has 0 <= c <= 1 (false for NaN and inf) and its valid value is on.  Its luma is
+ *             I = (0.299 R + 0.587 G) + 0.114 B, fp32, one rounding per operation.  gx = 0.5 (I[y,x+1] - I[y,x-1]) is
+ *             valid iff both of those pixels are valid, gy = 0.5 (I[y+1,x] - I[y-1,x]) likewise: the image border has no
+ *             gradient.  Output planes [3,H,W] = (I, gx, gy).  k_depth_normal marks a pixel without a normal by a value no
+ *             normal has, (0,0,0); in the same way an invalid I is written as -1 and an invalid gx or gy as 2, values no
+ *             valid one has (0 <= I <= 1 + 2^-22, |g| <= 0.5 + 2^-23).  A reader takes I as valid iff I >= 0 and a
+ *             gradient iff |g| <= 1, both false for a NaN.
+ *   Rows      (k_icp_rows_rgbd; grid and lane mapping of k_icp_rows).  Steps 1 - 4 of "Rows" above, with the continuous
+ *             position kept: x' = mfx (p_0 / p_2) + mcx, y' = mfy (p_1 / p_2) + mcy, u' = rintf(x'), v' = rintf(y').  A pixel
+ *             that passes step 4 then gets BOTH rows, each under its own gates: the photometric row does not depend on
+ *             steps 5 - 7 (a ray cast has colour exactly where it has depth, and a frame whose geometric match is rejected
+ *             by distance or normal still constrains the in-plane motion), the geometric row and its seven counters are
+ *             steps 5 - 9 unchanged, with today's bits.  A pixel that fails steps 1 - 4 enters no photometric counter.
+ *             P1 I_s = intensity[0,v,u] must be valid, else PHOTO_INVALID.
+ *             P2 x0 = floorf(x'), y0 = floorf(y').  PHOTO_INVALID unless |x0|, |y0| < 2^23 (in float, before the conversion)
+ *                and 0 <= x0, x0 + 1 < model_width, 0 <= y0, y0 + 1 < model_height: nothing is loaded before this test.
+ *                The four neighbours (y0,x0), (y0,x0+1), (y0+1,x0), (y0+1,x0+1) must be valid in I, gx and gy, else
+ *                PHOTO_INVALID.  With ax = x' - x0, ay = y' - y0 (exact) a plane f is sampled as
+ *                top = f00 + ax (f01 - f00), bot = f10 + ax (f11 - f10), f_m = top + ay (bot - top): I_m, gx_m, gy_m.
+ *             P3 r_I = I_m - I_s.  a = gx_m mfx, b = gy_m mfy; J_p = (a / p_2, b / p_2, -(((a p_0 + b p_1) / p_2) / p_2));
+ *                J = [J_p ; p x J_p] with p x J_p = (p_1 J_p2 - p_2 J_p1, p_2 J_p0 - p_0 J_p2, p_0 J_p1 - p_1 J_p0);
+ *                w_i = lambda J_i (i < 6), w_6 = lambda r_I.  One rounding per operation, left to right as written.
+ *             P4 PHOTO_BOUND unless every |w_i| < 16 (false for a NaN): fx / p_2 is unbounded at close range, so this is a
+ *                gate per pixel and not an argument check.  The pixel's geometric row still counts.
+ *             P5 PHOTO_ACCEPTED: the 28 products w_i w_j enter THE SAME 28 sums as trunc(v * 2^30), and trunc((r_I r_I) *
+ *                2^30) enters the sum of r_I^2.
+ *   Sums      MGS_ICP_RGBD_SUMS = 39 words: the 35 of MGS_ICP_SUMS, then PHOTO_ACCEPTED, PHOTO_INVALID, PHOTO_BOUND and the
+ *             fixed-point sum of r_I^2.  Bound: a geometric product is below 2^10 (above), a photometric one below 16 * 16
+ *             = 2^8, so a pixel adds less than 2^10 + 2^8 = 1.25 * 2^10 to a sum, in fixed point 1.25 * 2^40, and 2^22
+ *             pixels less than 1.25 * 2^62 < 2^63.  r_I^2 <= (1 + 2^-21)^2 stays below 2^53.
+ *   Solve     k_icp_solve's arithmetic on the combined sums.  MGS_ICP_TOO_FEW tests accepted + photo_accepted <
+ *             min_pixels: a frame with texture and little valid geometry can still align.
+ *   Outputs   those of mgs_icp_align; the record's words 52 .. 55 hold PHOTO_ACCEPTED, PHOTO_INVALID, PHOTO_BOUND and the
+ *             sum of r_I^2, the history row's word 7 the sum of r_I^2 (its word 1 is the combined sum of r^2, the
+ *             photometric part weighted by lambda^2).  `intensity` [3,H,W] and `model_intensity` [3,Hm,Wm] are written
+ *             once per call, before the first iteration.
+ * Launches: two of k_icp_intensity, one to start, then k_icp_rows_rgbd and the solve per iteration, all enqueued at once.
+ * Refused with MGS_ERR_BAD_ARGUMENT, beside what mgs_icp_align refuses: a null image, model_color, intensity or
+ * model_intensity, a layout flag outside {0, 1}, photo_weight NaN, negative or above MGS_ICP_PHOTO_WEIGHT_MAX (1024: with
+ * |r_I| <= 1 + 2^-21 a larger one could only trip the gate).  3 * width * height >= 2^31: MGS_ERR_UNSUPPORTED. */
+#define MGS_ICP_RGBD_SUMS 39
+#define MGS_ICP_PHOTO_WEIGHT_MAX 1024.0f
+
+typedef struct mgs_icp_intensity_args {
+  int32_t width, height;
+  int32_t chw;                           /* 0: rgb is [H,W,3], 1: [3,H,W] */
+  int32_t reserved0;
+  const float* rgb;
+  const float* valid;                    /* [H,W]: on where > 0, or NULL (all on) */
+  float* out;                            /* [3,H,W]: I, gx, gy */
+} mgs_icp_intensity_args;
+
+typedef struct mgs_icp_rgbd_args {
+  mgs_icp_args icp;                      /* as for mgs_icp_align; scratch is mgs_icp_rgbd_scratch_bytes(total iterations) */
+  float photo_weight;                    /* lambda, in [0, MGS_ICP_PHOTO_WEIGHT_MAX] */
+  int32_t image_chw;                     /* the layout of `image` */
+  int32_t model_color_chw;               /* the layout of `model_color` */
+  int32_t reserved0;
+  const float* image;                    /* the sensor's RGB */
+  const float* model_color;              /* the model view's RGB; valid where model_depth > 0 */
+  float* intensity;                      /* [3,H,W] out */
+  float* model_intensity;                /* [3,Hm,Wm] out */
+} mgs_icp_rgbd_args;
+
+int32_t mgs_icp_intensity_args_size(void);
+int32_t mgs_icp_rgbd_args_size(void);
+uint64_t mgs_icp_rgbd_scratch_bytes(int32_t max_iterations_total);   /* partial rows of 39 words, then the history */
+int32_t mgs_icp_intensity(const mgs_icp_intensity_args* args, void* stream);
+int32_t mgs_icp_align_rgbd(const mgs_icp_rgbd_args* args, void* stream);
+
 /* ---- mesh clean-up ("Mesh clean-up") -------------------------------------------------------------------
  * Connected components of an indexed triangle mesh (verts [V,3] f32, faces [F,3] i32, colors [V,3] f32 or NULL),
  * clusters kept by size, vertices / colours / faces compacted.  The NumPy mirror mesh_clean.clean_mesh_numpy is the

@@ -51,6 +51,8 @@ EXPORTS = (
     "mgs_tsdf_raycast_args_size", "mgs_sparse_tsdf_raycast_args_size", "mgs_raycast_shade_args_size",
     "mgs_sparse_tsdf_raycast_scratch_bytes", "mgs_tsdf_raycast", "mgs_sparse_tsdf_raycast", "mgs_raycast_shade",
     "mgs_icp_args_size", "mgs_icp_scratch_bytes", "mgs_icp_align",
+    "mgs_icp_intensity_args_size", "mgs_icp_rgbd_args_size", "mgs_icp_rgbd_scratch_bytes", "mgs_icp_intensity",
+    "mgs_icp_align_rgbd",
     "mgs_mesh_clean_args_size", "mgs_mesh_clean_scratch_bytes", "mgs_mesh_clean_count", "mgs_mesh_clean_emit",
     "mgs_mesh_components",
     "mgs_surface_sample_args_size", "mgs_surface_sample_scratch_bytes", "mgs_surface_sample",
@@ -476,6 +478,19 @@ class IcpArgs(C.Structure):
                                       "D", "record")])
 
 
+ICP_RGBD_SUMS, ICP_PHOTO_WEIGHT_MAX = 39, 1024.0      # MGS_ICP_RGBD_SUMS, MGS_ICP_PHOTO_WEIGHT_MAX
+
+
+class IcpIntensityArgs(C.Structure):
+    _fields_ = ([(n, C.c_int32) for n in ("width", "height", "chw", "reserved0")]
+                + [(n, _fp) for n in ("rgb", "valid", "out")])
+
+
+class IcpRgbdArgs(C.Structure):
+    _fields_ = [("icp", IcpArgs), ("photo_weight", C.c_float), ("image_chw", C.c_int32), ("model_color_chw", C.c_int32),
+                ("reserved0", C.c_int32)] + [(n, _fp) for n in ("image", "model_color", "intensity", "model_intensity")]
+
+
 MESH_CLEAN_MAX_ITEMS = (2 ** 31 - 1) // 3     # 3 V, 3 F < 2^31: 32-bit element indices of the [n,3] arrays
 MESH_CLEAN_COUNTS = 5                         # V', F', clusters, kept clusters, bad faces
 
@@ -811,6 +826,13 @@ def lib():
         raise NativeLibraryError("IcpArgs does not have the size of mgs_icp_args")
     L.mgs_icp_scratch_bytes.restype, L.mgs_icp_scratch_bytes.argtypes = C.c_uint64, [C.c_int32]
     L.mgs_icp_align.restype, L.mgs_icp_align.argtypes = C.c_int32, [C.POINTER(IcpArgs), C.c_void_p]
+    for size, cls, fn in ((L.mgs_icp_intensity_args_size, IcpIntensityArgs, L.mgs_icp_intensity),
+                          (L.mgs_icp_rgbd_args_size, IcpRgbdArgs, L.mgs_icp_align_rgbd)):
+        size.restype, size.argtypes = C.c_int32, []
+        if size() != C.sizeof(cls):
+            raise NativeLibraryError(f"{cls.__name__} does not have the size of its C struct")
+        fn.restype, fn.argtypes = C.c_int32, [C.POINTER(cls), C.c_void_p]
+    L.mgs_icp_rgbd_scratch_bytes.restype, L.mgs_icp_rgbd_scratch_bytes.argtypes = C.c_uint64, [C.c_int32]
     L.mgs_mesh_clean_args_size.restype, L.mgs_mesh_clean_args_size.argtypes = C.c_int32, []
     if L.mgs_mesh_clean_args_size() != C.sizeof(MeshCleanArgs):
         raise NativeLibraryError("MeshCleanArgs does not have the size of mgs_mesh_clean_args")

@@ -230,7 +230,9 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     which takes `icp_kw`); the tracker's camera starts from the ICP pose when its status is converged or out of
     iterations, else from the previous pose as without it - chosen on the device by the status word, no host read, inside
     the timed tracking section.  The result then also holds `icp_records`: {frame id: icp.read_record's dict}, read once
-    after the run.  False makes no ICP or ray-cast call."""
+    after the run.  icp_kw=dict(photo_weight=...) > 0 adds the photometric rows (icp.align's RGB-D path): the camera's
+    original_image goes with the depth, the volume must have been fused with colour (it is, from a sensor depth with an
+    image), and the records carry "photo" and "sum_ri2".  False makes no ICP or ray-cast call."""
     if icp_init and (mesh_volume is None or not (sensor_depth or stereo_matcher is not None)):
         raise ValueError("icp_init needs mesh_volume and a sensor or stereo depth (sensor_depth=True or a stereo_matcher)")
     if icp_init and stereo_matcher is None and any(f.depth is None for f in frames):
@@ -358,7 +360,10 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     def icp_start(k, fr, vp, T_prev):
         """vp.T <- the ICP pose of the frame against the volume's ray cast at T_prev, if its status is ok (on the device)."""
         from . import icp as _icp
-        res = _icp.track_against_volume(mesh_volume, depth_of(fr), T_prev, vp, read=False, **(icp_kw or {}))
+        kw = dict(icp_kw or {})
+        if float(kw.get("photo_weight", 0.0)) > 0.0:      # RGB-D alignment: the camera's image against the ray cast's colour
+            kw.setdefault("image", vp.original_image)
+        res = _icp.track_against_volume(mesh_volume, depth_of(fr), T_prev, vp, read=False, **kw)
         with torch.no_grad():
             vp.T.copy_(_icp.select_pose(res, vp.T))
         icp_raw[k] = res["record"]
@@ -479,7 +484,8 @@ def run_sequence(frames, cam, dev, *, sensor_depth: bool = False, kf_interval: i
     if icp_init:
         from .icp import read_record
         words = torch.stack([icp_raw[k] for k in sorted(icp_raw)]).cpu().numpy() if icp_raw else []
-        result["icp_records"] = {k: read_record(w) for k, w in zip(sorted(icp_raw), words)}
+        rgbd = float((icp_kw or {}).get("photo_weight", 0.0)) > 0.0
+        result["icp_records"] = {k: read_record(w, rgbd=rgbd) for k, w in zip(sorted(icp_raw), words)}
     return result
 
 

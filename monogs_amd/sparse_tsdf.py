@@ -310,6 +310,7 @@ class SparseTSDFVolume:
         self.tsdf = torch.ones((cap, BRICK_POINTS), device=self.dev)
         self.weight = torch.zeros((cap, BRICK_POINTS), device=self.dev)
         self.color = torch.zeros((3, cap, BRICK_POINTS), device=self.dev)
+        self.has_color = False          # whether a view was integrated with an image (host-side: no read of the planes)
         self.brick_coords = torch.zeros((cap, 3), dtype=torch.int32, device=self.dev)
         self.map_keys = torch.full((self.table_size,), -1, dtype=torch.int64, device=self.dev)
         self.map_vals = torch.zeros(self.table_size, dtype=torch.int32, device=self.dev)
@@ -323,6 +324,7 @@ class SparseTSDFVolume:
         self.tsdf.fill_(1.0)
         self.weight.zero_()
         self.color.zero_()
+        self.has_color = False
         self.map_keys.fill_(-1)
         self.state.zero_()
         self.brick_epoch += 1
@@ -401,6 +403,7 @@ class SparseTSDFVolume:
                 raise ValueError(f"image must be [3,{H},{W}], got {tuple(image.shape)}")
             a.image = image.data_ptr()
             keep.append(image)
+            self.has_color = True
         L = _cabi.lib()
         if allocate:
             key = (W, H, a.samples)
@@ -480,10 +483,11 @@ class SparseTSDFVolume:
         from .tsdf_raycast import raycast_view
         return raycast_view(self, camera, **kw)
 
-    def track(self, depth, T_prev, view, **kw):
-        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it."""
+    def track(self, depth, T_prev, view, image=None, photo_weight=0.0, **kw):
+        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it - with `image`
+        [3,H,W] and photo_weight > 0 also its colour (a volume fused without colour then raises ValueError)."""
         from .icp import track_against_volume
-        return track_against_volume(self, depth, T_prev, view, **kw)
+        return track_against_volume(self, depth, T_prev, view, image=image, photo_weight=photo_weight, **kw)
 
     # ---- to and from dense planes (torch indexing; for tests and users, not on a hot path) ---------------------------
     def to_dense(self, lo=None, dims=None):
@@ -567,6 +571,7 @@ class SparseTSDFVolume:
         if color is not None:
             for c in range(3):
                 vol.color[c, :B] = rows(torch.as_tensor(color, dtype=torch.float32)[c], 0.0)
+            vol.has_color = True
         vol.brick_coords[:B] = torch.as_tensor(bricks, dtype=torch.int32).to(dev)
         v = _cabi.SparseTsdfVolume()
         vol._volume(v)

@@ -237,6 +237,7 @@ class TSDFVolume:
         self.tsdf = torch.ones(shape, device=self.dev)
         self.weight = torch.zeros(shape, device=self.dev)
         self.color = torch.zeros((3,) + shape, device=self.dev)
+        self.has_color = False          # whether a view was integrated with an image (host-side: no read of the planes)
         self._scratch = None
         self._counts = torch.zeros(2, dtype=torch.int32, device=self.dev)
 
@@ -258,6 +259,7 @@ class TSDFVolume:
         self.tsdf.fill_(1.0)
         self.weight.zero_()
         self.color.zero_()
+        self.has_color = False
 
     def _plane(self, t, shape, what):
         if t.device != self.dev or t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != shape:
@@ -297,6 +299,7 @@ class TSDFVolume:
                 raise ValueError(f"image must be [3,{H},{W}], got {tuple(image.shape)}")
             a.image = image.data_ptr()
             keep.append(image)
+            self.has_color = True
         shape = (self.nz, self.ny, self.nx)
         a.tsdf, a.wsum = self._plane(self.tsdf, shape, "tsdf"), self._plane(self.weight, shape, "weight")
         a.color = self._plane(self.color, (3,) + shape, "color")
@@ -415,10 +418,11 @@ class TSDFVolume:
         from .tsdf_raycast import raycast_view
         return raycast_view(self, camera, **kw)
 
-    def track(self, depth, T_prev, view, **kw):
-        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it."""
+    def track(self, depth, T_prev, view, image=None, photo_weight=0.0, **kw):
+        """icp.track_against_volume: ray cast this volume at T_prev and align the sensor plane `depth` to it - with `image`
+        [3,H,W] and photo_weight > 0 also its colour (a volume fused without colour then raises ValueError)."""
         from .icp import track_against_volume
-        return track_against_volume(self, depth, T_prev, view, **kw)
+        return track_against_volume(self, depth, T_prev, view, image=image, photo_weight=photo_weight, **kw)
 
 
 def sparse_volume(sparse, voxel_size: float, device, trunc=None, max_weight: float = 64.0):

@@ -12,7 +12,10 @@ schedule (both kernels from the library's events, and the wall time of a one-ite
 enqueued at once (wall, with one synchronise at the end and no host read), track_against_volume on the dense and the sparse
 volume, and for scale one first-order NativeTracker iteration of the same build on the same map.  raycast(), integrate()
 and the tracking iteration are printed next to what profiles/tsdf_raycast_profile.txt and the README recorded before this
-kernel existed: nothing in their code changed.  Wall times are medians of warm calls, each ended by a synchronise; kernel
+kernel existed: nothing in their code changed.  The RGB-D legs (icp.align(image=, photo_weight=): k_icp_intensity twice per
+call, k_icp_rows_rgbd and k_icp_solve_rgbd per iteration) follow on the wavy scene, re-fused with the texture of
+tests/icp_rgbd_cases.py AFTER its geometric legs were measured as before: the rows kernel per stride, the default schedule,
+and track_against_volume dense and sparse, to be read against the geometric legs of the same run.  Wall times are medians of warm calls, each ended by a synchronise; kernel
 times are means over five warm calls.  No threshold is set anywhere: the numbers are written down.  One human-readable line
 per measurement, then one JSON line."""
 import json
@@ -53,6 +56,8 @@ def measure(name, vol, sensor, T_prev, vt, z_far, akw, levels, rec, lines):
     rec["track_against_volume_kernels_us"] = CP.kernels_us(track)
     rec["result"] = {"status": info["status_name"], "iterations_run": info["iterations_run"], "counts": info["counts"],
                      "ran": [int(v) for v in info["history"]["ran"]]}
+    if "photo" in info:
+        rec["result"]["photo"] = info["photo"]
     lines.append(f"{name}: track_against_volume (ray cast at the previous pose, sensor normals, the default schedule enqueued at once, "
                  f"no host read) {rec['track_against_volume_wall_us']:.0f} us (wall), kernels (means per launch, idle launches "
                  f"included) {rec['track_against_volume_kernels_us']}; {rec['result']}")
@@ -130,6 +135,26 @@ def main():
         rec["pose_error"] = {"start_m_deg": IC.pose_error(torch.eye(4).numpy(), IC.true_pose()), "end_m_deg": (et, er)}
         lines.append(f"{name}: the frame starts {rec['pose_error']['start_m_deg']} (m, degrees) off and ends {rec['pose_error']['end_m_deg']} off")
         out[name] = rec
+    # RGB-D: the same volumes fused again with colour, the same frame with its image, photo_weight 1
+    import icp_rgbd_cases as RC
+    image = RC.painted(frame.cpu(), IC.true_pose(), intr).to(dev)
+    # fused from wider views (880 x 660, the same f), so that the border of the fused region, where a ray cast's colour
+    # darkens, lies outside the tracked view - as tests/icp_rgbd_cases.py does at its size
+    wide, views = (548.0, 548.0, 439.5, 329.5), []
+    for T in IC.fusion_poses():
+        depth = IC.surface_depth(T, 660, 880, wide)
+        views.append((torch.from_numpy(T).float().to(dev), depth.to(dev), RC.painted(depth, T, wide).to(dev)))
+    for name, vol in volumes:
+        vol.reset()
+        for T, depth, img in views:
+            vol.integrate(depth, T, *wide, image=img)
+        rec = {}
+        res = measure(name + "_rgbd", vol, frame, eye, (eye, *intr, H, W), IC.Z_FAR, dict(read=False, image=image, photo_weight=1.0),
+                      name == "wavy_dense", rec, lines)
+        et, er = IC.pose_error(res["info"]["T_w2c"], IC.true_pose())
+        rec["pose_error"] = {"end_m_deg": (et, er)}
+        lines.append(f"{name}_rgbd: with the photometric rows the frame ends {rec['pose_error']['end_m_deg']} (m, degrees) off")
+        out[name + "_rgbd"] = rec
     # for scale: one first-order tracking iteration of the same build on the same map
     from monogs_amd.slam_loops import ViewCamera
     vp = ViewCamera(1, pkg["render"], T_prev, view.projection_matrix, view.FoVx, view.FoVy, H, W, dev, intrinsics=cam)
