@@ -215,7 +215,8 @@ def stereo_sgbm_numpy(left_u8, right_u8, *, numDisparities=NUM_DISPARITIES, bloc
       pixel cost  Birchfield-Tomasi on g and on the raw intensity.  For u at x (neighbours clamped): ul = (u+u[x-1])//2,
                   ur = (u+u[x+1])//2, u0 = min(u,ul,ur), u1 = max(u,ul,ur); likewise for v = R[x-d];
                   c = min(max(0, u-v1, v0-u), max(0, v-u1, u0-v)) >> 2; the cost is the sum over the two channels (<= 70).
-      block cost  C(x,y,d): the pixel cost over |dx| <= r, |dy| <= r, y clamped to [0,H-1], x to [D,W-1] (<= 30 870).
+      block cost  C(x,y,d): the pixel cost over |dx| <= r, |dy| <= r, y clamped to [0,H-1], x to [D,W-1]
+                  (<= (2r+1)^2 * 70: 30 870 at blockSize 20, 58 870 at 29, the largest the device takes).
       paths       five: the predecessor q of p = (x,y) is (x-1,y), (x+1,y), (x-1,y-1), (x,y-1) or (x+1,y-1);
                   L(p,d) = C(p,d) + min(L(q,d), L(q,d-1)+P1, L(q,d+1)+P1, m_q+P2) - m_q with m_q = min_d L(q,d) and
                   d-1 / d+1 outside 0..D-1 left out; q outside the valid region: L(p,.) = C(p,.).  S = their sum.

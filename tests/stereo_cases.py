@@ -53,13 +53,34 @@ def ramp_pair(H=37, W=203, seed=5):
     return q(left), q(canvas[:, D:D + W])
 
 
+def offset_pair(H, W, lift=190, span=66, seed=5):
+    """The ramp pair squeezed into `span` grey levels (a * span // 256) with `lift` added to the left image only: the
+    brightness offset makes every pixel cost large - the block cost at r = 14 reaches or passes 32 768, see OFFSET_LIFT -
+    while the texture keeps the argmin structured.  Returns (left, right), both uint8."""
+    assert 0 <= lift and lift + (255 * span) // 256 <= 255
+    left, right = (a.astype(np.int64) * span // 256 for a in ramp_pair(H, W, seed))
+    return np.ascontiguousarray((left + lift).astype(np.uint8)), np.ascontiguousarray(right.astype(np.uint8))
+
+
+# offset_pair's lift by pair name.  At 190 EVERY valid entry of C at r = 14 is above 32 767 (37 060 .. 42 393 at the sizes
+# tested): the volumes' upper half, but all 64 disparities of a pixel on one side of bit 15.  At 155 and 157 C runs from
+# about 30 000 to 35 000 and most pixels have disparities on both sides: 21 % and 78 % of the entries are above at
+# 37x203, 29 % and 78 % at 33x129.
+OFFSET_LIFT = {"offset": 190, "straddle_low": 155, "straddle_high": 157}
+
+
 @functools.lru_cache(maxsize=None)
 def pair(name, H=None, W=None):
-    """(left, right) uint8, read-only: "planes", "ramp", or "noise" at H x W (two unrelated images)."""
+    """(left, right) uint8, read-only: "planes", "ramp", a name of OFFSET_LIFT (`offset_pair` at H x W with that lift),
+    or "noise" at H x W (two unrelated images)."""
+    if name not in ("planes", "ramp") and (H is None or W is None):
+        raise ValueError(f'pair("{name}") needs H and W')
     if name == "planes":
         out = planes_pair()[:2]
     elif name == "ramp":
         out = ramp_pair() if H is None else ramp_pair(H, W)
+    elif name in OFFSET_LIFT:
+        out = offset_pair(H, W, lift=OFFSET_LIFT[name])
     elif name == "noise":
         out = noise(H, W, 11), noise(H, W, 12)
     else:
@@ -70,10 +91,20 @@ def pair(name, H=None, W=None):
 
 
 @functools.lru_cache(maxsize=None)
-def mirror(name, H=None, W=None):
-    """stereo_sgbm_numpy(..., return_flags=True) of `pair(name, H, W)`: (disp16, depth, not_unique, failed_left_right),
-    computed once and read-only."""
-    out = SD.stereo_sgbm_numpy(*pair(name, H, W), return_flags=True)
+def mirror(name, H=None, W=None, *, blockSize=SD.BLOCK_SIZE, uniquenessRatio=SD.UNIQUENESS_RATIO):
+    """stereo_sgbm_numpy(..., return_flags=True) of `pair(name, H, W)` at the block size and uniqueness ratio given:
+    (disp16, depth, not_unique, failed_left_right), computed once per setting and read-only."""
+    out = SD.stereo_sgbm_numpy(*pair(name, H, W), blockSize=blockSize, uniquenessRatio=uniquenessRatio,
+                               return_flags=True)
     for a in out:
         a.setflags(write=False)
     return out
+
+
+@functools.lru_cache(maxsize=None)
+def mirror_block_cost(name, H=None, W=None, r=SD.BLOCK_SIZE // 2):
+    """The mirror's C of `pair(name, H, W)` at half block r: block_cost_numpy(pixel_cost_numpy(L, R), r), int32
+    [H,W,64], read-only.  For the preconditions that a test states on the reference side."""
+    C_ = SD.block_cost_numpy(SD.pixel_cost_numpy(*pair(name, H, W)), r)
+    C_.setflags(write=False)
+    return C_
